@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the MokA adapter hot path on MI355X (contract: see the task statement).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--seq S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--seq S] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch: adapter forward + backward of all
 7 x 32 adapted projections of Llama-2-7B (r = 16, 3 modalities, AVT semantics) on B synthetic
@@ -16,8 +16,10 @@ are NOT part of the hot path (they run on stock PyTorch-ROCm); their outputs / i
 gradients are the in/out operands of the kernels and are resident in HBM before the clock
 starts.
 
-Prints ONE JSON line on rank 0 (metric of BASELINE.json, `roofline` for the dominant kernel,
-`cpu_baseline` = the oracle port on the host cores, bounded sample).
+Prints ONE JSON line on rank 0 (metric of BASELINE.json, `ms_per_step`).  A plain run sets up, warms up, times the
+steps and prints the line; --full also measures what takes runs of its own: `roofline` for the dominant kernel, the
+per-kernel table, the in-schedule ablation and `cpu_baseline` (the oracle port on the host cores, bounded sample).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -526,11 +528,57 @@ def end_to_end(args, dev):
     return res
 
 
-def main():
+DUMP_BYTES = 60 << 20          # --dump-outputs: float32 bytes in all (with the .npy headers: under 64 MB, 10^6 or 2^20 bytes each)
+
+
+def step_outputs(wl, with_optimizer):
+    """What a caller of the timed step receives, by name: the y and dx buffers the step updates in place (every chain, every activation
+    set, every projection / input), and the fp32 master parameters after the optimizer update -- the flat gradient with --no-optimizer."""
+    outs = []
+    for ci, (sets, _, _, _) in enumerate(wl["keep"]):
+        for si, (_, dacts, ys) in enumerate(sets):
+            outs += [(f"y.chain{ci}.set{si}.{name}", y) for (name, _, _, _), y in zip(PROJS, ys)]
+            outs += [(f"dx.chain{ci}.set{si}.{k}", dx) for k, dx in dacts.items()]
+    outs.append(("params", wl["master"]) if with_optimizer else ("grad", wl["gbuf"]))
+    return outs
+
+
+def dump_outputs(outs, path, budget=DUMP_BYTES, seed=20240611):
+    """Write every (name, tensor) of `outs` as path/<name>.npy in float32.  Each output gets an equal share of `budget`; one larger than its
+    share is written as a fixed sample of its elements (flat indices drawn from a generator seeded by `seed` and the output's position,
+    sorted), so that two runs with the same arguments write the same elements.  Returns the bytes written."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = budget // 4 // max(1, len(outs))
+    total = 0
+    for i, (name, t) in enumerate(outs):
+        flat = t.detach().reshape(-1)
+        if flat.numel() > share:
+            g = torch.Generator().manual_seed(seed + i)
+            idx = torch.randint(flat.numel(), (share,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        arr = flat.float().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), arr)
+        total += arr.nbytes
+    return total
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=120, help="timed steps (default: ~4 s of GPU work, long enough for an external busy sampler to see it)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline (`cpu_baseline`), the dominant kernel's roofline and the "
+                         "per-kernel table from extra live passes (`roofline`, `entry_point_ms_per_pass`, `kernels`), the in-schedule ablation of the "
+                         "dominant family (`roofline.in_schedule`) and the host time of one replay (`graph_replay_host_ms`).  Implied by "
+                         "--verify-graph, --probe-forward, --e2e and an explicit --ablate other than off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left in the buffers a caller receives (y and dx of every chain / activation "
+                         "set, the fp32 parameters after the optimizer update or the gradient with --no-optimizer) as DIR/<name>.npy, float32, at "
+                         "most 64 MB in all (a fixed sample of the larger ones); the inputs are seeded, so the same arguments give the same inputs.  "
+                         "The order of the fp32 gradient atomics varies, and the optimizer steps carry that into the weights: two runs of the default "
+                         "command agree to ~2e-3 relative on y / dx; with --no-optimizer y / dx agree to 1e-6")
     ap.add_argument("--batch", type=int, default=4, help="sequences per GPU (reference AVT micro-batch: ft_musicavqa.sh:12-13)")
     ap.add_argument("--seq", type=int, default=2048)
     ap.add_argument("--rank", type=int, default=16)
@@ -628,12 +676,21 @@ def main():
                          "same activation state; y / dx must agree bit for bit, the flat gradient to its atomics' spread -> `graph_check`")
     ap.add_argument("--probe-forward", action="store_true",
                     help="also time the forward alone as a hipGraph of its own against the same launches live (HIP events, no profiler) -> `forward_only`")
-    ap.add_argument("--ablate", default="dominant",
-                    help="in-schedule marginals: dominant (default) = the dominant kernel family only -> roofline.in_schedule; all / a comma list of "
-                         "moka_amd.schedule.FAMILIES -> also the `ablation` table; off")
+    ap.add_argument("--ablate", default=None,
+                    help="in-schedule marginals: dominant (the default with --full) = the dominant kernel family only -> roofline.in_schedule; all / "
+                         "a comma list of moka_amd.schedule.FAMILIES -> also the `ablation` table; off (the default without --full)")
     ap.add_argument("--no-group", action="store_true",
                     help="launch every projection on its own (the grouped entry points let q/k/v and gate/up share x / dx)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.verify_graph or args.probe_forward or args.e2e or args.ablate not in (None, "off"):
+        args.full = True
+    if args.ablate is None:
+        args.ablate = "dominant" if args.full else "off"
+    return args
+
+
+def main():
+    args = parse_args()
     if args.layers is None:
         args.layers = MODELS[args.model]["layers"]
     if args.graph == "auto":
@@ -720,6 +777,7 @@ def main():
     if args.buckets == 0 and comm and tail == 0:
         sizes = geometric_buckets(args.layers)
     nb = args.buckets if args.buckets > 0 else 8
+    torch.manual_seed(0)                             # (the same arguments build the same synthetic inputs and parameters: --dump-outputs compares runs)
     wl = build_workload(args, dev, lib, lambda n, ends: FlatGradBucket(n, ends, dev, n_buckets=nb, comm_dtype=torch.bfloat16 if args.comm_bf16 else None,
                                                                        force_comm=args.force_comm, tail_layers=tail or None, bucket_sizes=sizes),
                         chains=args.chains)
@@ -747,8 +805,10 @@ def main():
     sched = SCH.GraphedAdapterStep(wl, make_cfg(), L, optimizer=opt, world=world, comm=comm, device=dev)
     opt_in_bwd, shadows_main, shadows_opt = sched.opt_in_bwd, sched.shadows_main, sched.shadows_opt
 
-    records = Recorder(only=LIVE, every=args.bracket_every)
-    records.reserve(2 * len(wl["units"]) * args.steps + 16)
+    records = None                                   # (--full: the dominant kernel's launches bracketed with HIP events -> `roofline`)
+    if args.full:
+        records = Recorder(only=LIVE, every=args.bracket_every)
+        records.reserve(2 * len(wl["units"]) * args.steps + 16)
 
     sched.capture()                                  # (falls back to live launches, and says so, if the capture fails)
     args.graph = sched.graph_mode                    # (what the line reports is what ran)
@@ -778,10 +838,14 @@ def main():
     ms_per_step = el * 1e3 / args.steps
     tokens_per_s = world * T * args.steps / el
 
+    # what the last timed step left for its caller, before anything below launches into the same buffers
+    if args.dump_outputs and rank == 0:
+        dump_outputs(step_outputs(wl, opt is not None), args.dump_outputs)
+
     # host side of a replay: how long hipGraphLaunch keeps the launching thread for ONE step (idle GPU in front of it, so nothing blocks on
     # a full queue) against the step on the GPU -- a multi-branch graph is replayed node by node, and a step whose replay takes the host
     # longer than the GPU needs is host-bound
-    replay_host_ms = sched.replay_host_ms() if rank == 0 else None
+    replay_host_ms = sched.replay_host_ms() if (rank == 0 and args.full) else None
 
     # --verify-graph: the captured schedule (chains on forked streams, deferred dA_m on the hub, whatever the executor makes of it) against the
     # same launches live, one chain after the other on ONE stream, from the same activation state: y and dx bit for bit (deterministic
@@ -919,88 +983,7 @@ def main():
     if rank == 0:
         fwd_b, bwd_b = algorithmic_bytes_per_token(MODELS[args.model], args.rank, args.layers)
         algo_gbs = (fwd_b + bwd_b) * T / (ms_per_step * 1e-3) / 1e9
-        # per-launch durations from the HIP events recorded on the launch stream inside the timed region
-        def collect(items):
-            tot = {n: 0.0 for n in ENTRY}
-            cnt = {n: 0 for n in ENTRY}
-            byt = {n: 0 for n in ENTRY}
-            per_shape = {}
-            for n, u, e0, e1 in items:
-                ms = e0.elapsed_time(e1)
-                tot[n] += ms
-                cnt[n] += 1
-                byt[n] += u.algo[n]
-                key = (n, u.label, u.d_in, tuple(u.d_outs))
-                a_, b_, _ = per_shape.get(key, (0.0, 0, 0))
-                per_shape[key] = (a_ + ms, b_ + 1, u.algo[n])
-            return tot, cnt, byt, per_shape
-        sp_ = c_void_p(torch.cuda.current_stream().cuda_stream)
         units_all = wl["units"]
-        roof_behind = not records.items
-        if not records.items:
-            # graph replay: nothing can be bracketed inside the timed region -> the dominant entry point is bracketed (every n-th
-            # launch, as in the live mode) in extra live passes right behind it, same buffers, same kernel sequence
-            for _ in range(min(args.steps, 3)):
-                sched.live_pass(sp_, records, None)
-            torch.cuda.synchronize()
-        tot, cnt, byt, per_shape = collect(records.items)         # the dominant entry point (LIVE)
-        # every entry point, in one extra untimed pass (full bracketing would perturb the timed region)
-        extra = Recorder()
-        sched.live_pass(sp_, extra, extra)
-        if shadows_opt:
-            run_shadows(lib, wl, sp_, range(L), extra)
-        torch.cuda.synchronize()
-        tot_x, cnt_x, byt_x, per_shape_x = collect(extra.items)
-        # the forward alone, replayed as a hipGraph of its own against the same launches live: HIP events around whole passes, no
-        # profiler (profiles/README.md: do the 8-25 us gaps rocprofv3 shows in front of the forward kernels of a graph replay exist?)
-        fwd_only = None
-        if args.probe_forward and args.chains == 1:
-            try:
-                pst = torch.cuda.Stream(device=dev, priority=-1 if args.chain_priority == "high" else 0)
-                with torch.cuda.stream(pst):
-                    run_forward(lib, wl, c_void_p(pst.cuda_stream), shadows=shadows_main)
-                torch.cuda.synchronize()
-                fg = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(fg, stream=pst):
-                    run_forward(lib, wl, c_void_p(torch.cuda.current_stream().cuda_stream), shadows=shadows_main)
-                torch.cuda.synchronize()
-
-                def _timed(fn, n=6):
-                    fn()
-                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    a.record()
-                    for _ in range(n):
-                        fn()
-                    b.record()
-                    torch.cuda.synchronize()
-                    return a.elapsed_time(b) / n
-                g_ms = _timed(fg.replay)
-                l_ms = _timed(lambda: run_forward(lib, wl, sp_, None, shadows=shadows_main))
-                fwd_only = {"graph_ms": round(g_ms, 3), "live_ms": round(l_ms, 3), "launches": sum(2 if u.fused else 3 for u in units_all),
-                            "what": "forward pass alone, 6 passes between two HIP events: replay of a forward-only hipGraph vs the same launches live"}
-                del fg
-            except Exception as exc:                 # a probe, never a requirement
-                fwd_only = {"error": repr(exc)}
-        live_items = records.items
-        table = {}
-        for (n, label, di, dos), (ms, c_, nb) in sorted(per_shape_x.items()):
-            avg = ms / c_
-            table[f"{n}[{label}: {di}->{'/'.join(str(v) for v in dos)}]"] = {"avg_ms": round(avg, 4), "algo_GBps": round(nb / (avg * 1e-3) / 1e9, 1)}
-        # the dominant kernel: the largest entry point of a pass that is ONE kernel launch
-        # (moka_up_fwd -> moka_yt_kernel<RP> for the batched launches, moka_expand_kernel<.., true> for single projections; grouped units
-        #  run their members in one launch, grid z)
-        # the dominant KERNEL: every launch of moka_up_fwd is moka_yx_kernel<RP> where the whole stack runs the fused forward (the headline);
-        # otherwise the entry point is served by several kernels and the line names them
-        RPk = _lib.rank_pad(args.rank)
-        all_fused = all(u.fused for u in units_all)
-        any_fused = any(u.fused for u in units_all)
-        kern_name = ("moka_yx_kernel<%d>" % RPk) if all_fused else (
-            ("moka_yx_kernel<%d> (units %s) + " % (RPk, ", ".join(sorted({u.label for u in units_all if u.fused}))) if any_fused else "") +
-            "moka_yt_kernel<%d> / moka_expand_kernel<%d,NQ,true> (three-launch units)" % (RPk, RPk))
-        dom = "moka_up_fwd"
-        dom_bytes = byt[dom]
-        dom_avg_ms = tot[dom] / cnt[dom]
-        achieved = dom_bytes / cnt[dom] / (dom_avg_ms * 1e-3) / 1e9
         # the bytes THIS implementation has to move per step (grouped x / dx counted once per group, the deferred dA's second read of x
         # counted; rank-space tensors and weights left out as in the contract figure): forward x + y read-modify-write, backward gy +
         # dx read-modify-write + x again
@@ -1011,16 +994,6 @@ def main():
             actual_b += E * T * (u.d_in + 2 * sdo) + E * T * (sdo + 2 * u.d_in + u.d_in)
         actual_b *= args.layers
         actual_gbs = actual_b / (ms_per_step * 1e-3) / 1e9
-        traffic, traffic_src = None, None
-        if not args.no_traffic and (args.model, args.rank, args.variant) == ("7b", 16, "avt") and not args.no_group:
-            # (the PMC passes profile the headline workload; per launch = per layer / the layer's up-projection launches)
-            traffic, traffic_src = pmc_traffic_per_launch(T, wl["units_per_layer"])
-            if traffic is not None:
-                traffic = round(traffic / args.chains)   # (the PMC passes profile whole-batch launches; traffic is linear in the tokens)
-            if args.chains > 1 and traffic is not None:
-                traffic_src += " / %d (launches of %d tokens)" % (args.chains, T // args.chains)
-            elif traffic is not None:
-                traffic_src += " (measured on launches of %d tokens, scaled)" % json.load(open(PMC_TRAFFIC_FILE))["tokens"]
         out = {
             "metric": "tokens/sec/GPU Llama-2-7B MokA r=16 seq2048 bf16; adapter HBM %roofline" if (args.model, args.rank, args.seq) == ("7b", 16, 2048)
                       else "tokens/sec/GPU Llama-2-%s MokA r=%d seq%d bf16; adapter HBM %%roofline" % (args.model.upper(), args.rank, args.seq),
@@ -1047,7 +1020,7 @@ def main():
                             "grad_payload": "%s payload of the fp32 flat bucket, %d buckets, all-reduce on a side stream overlapped with the backward" % ("bf16" if args.comm_bf16 else "fp32", len(bucket.bucket_firsts())),
                             "bucket_layers": [len(bucket.bucket_layers(f)) for f in bucket.bucket_firsts()], "last_bucket_bytes": bucket.last_bucket_bytes(),
                             "adapter_params": wl["n_params"]},
-            "graph": args.graph, "graph_replay_host_ms": replay_host_ms, "graph_topology": ("hub" if args.hub else "chain") if not args.graph.startswith("off") else None,
+            "graph": args.graph, "graph_topology": ("hub" if args.hub else "chain") if not args.graph.startswith("off") else None,
             "graph_check": graph_check,
             "fused_forward": ("all units" if all(u.fused for u in units_all) else ("units " + ", ".join(sorted({u.label for u in units_all if u.fused})) if any(u.fused for u in units_all) else False)) if args.fused else False,
             "chains": args.chains,
@@ -1062,31 +1035,128 @@ def main():
             # what the bus really carries: this implementation's own bytes (x / dx of a group once, x a second time for the deferred dA)
             "adapter_actual_bytes_per_step": int(actual_b), "adapter_actual_GBps_per_gpu": round(actual_gbs, 1),
             "adapter_actual_hbm_frac": round(actual_gbs / HBM_PEAK_GBS, 4),
-            "roofline": {"bound": "hbm", "kernel": kern_name, "entry_point": "moka_up_fwd_fused" if all_fused else "moka_up_fwd",
-                         "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": round(dom_bytes / cnt[dom]),
-                         "avg_launch_ms": round(dom_avg_ms, 4), "launches_timed": cnt[dom],
-                         "where": ("live passes right behind the timed region (the timed region replays a hipGraph: nothing can be bracketed inside it)"
-                                   if roof_behind else "HIP events inside the timed region (every %d-th launch)" % args.bracket_every),
-                         "note": (None if args.chains == 1 else
-                                  "launches of %d tokens timed ALONE, the %d chains back to back on one stream; in the step they run beside the other chain's "
-                                  "launches (not observable inside a graph; rocprofv3 serialises the dispatches) -- adapter_hbm_roofline_frac is the step's figure"
-                                  % (T // args.chains, args.chains)),
-                         # the dominant family INSIDE the timed schedule (both chains, hub launches and all): marginal of leaving its launches out
-                         "in_schedule": (dict(kernel=kern_name, family="up_fwd", **ablation["families"]["up_fwd"], how=ablation["how"])
-                                         if (ablation and "up_fwd" in ablation["families"]) else None)},
-            "entry_point_ms_per_pass": {n: round(tot_x[n], 3) for n in ENTRY},
-            "forward_only": fwd_only,
-            "kernels": table,
+            "full": bool(args.full),
         }
-        if ablation is not None and args.ablate != "dominant":
-            out["ablation"] = ablation
+        if args.full:
+            # --full: the figures that take runs of their own.  Per-launch durations from the HIP events recorded on the launch stream
+            # inside the timed region
+            def collect(items):
+                tot = {n: 0.0 for n in ENTRY}
+                cnt = {n: 0 for n in ENTRY}
+                byt = {n: 0 for n in ENTRY}
+                per_shape = {}
+                for n, u, e0, e1 in items:
+                    ms = e0.elapsed_time(e1)
+                    tot[n] += ms
+                    cnt[n] += 1
+                    byt[n] += u.algo[n]
+                    key = (n, u.label, u.d_in, tuple(u.d_outs))
+                    a_, b_, _ = per_shape.get(key, (0.0, 0, 0))
+                    per_shape[key] = (a_ + ms, b_ + 1, u.algo[n])
+                return tot, cnt, byt, per_shape
+            sp_ = c_void_p(torch.cuda.current_stream().cuda_stream)
+            roof_behind = not records.items
+            if not records.items:
+                # graph replay: nothing can be bracketed inside the timed region -> the dominant entry point is bracketed (every n-th
+                # launch, as in the live mode) in extra live passes right behind it, same buffers, same kernel sequence
+                for _ in range(min(args.steps, 3)):
+                    sched.live_pass(sp_, records, None)
+                torch.cuda.synchronize()
+            tot, cnt, byt, per_shape = collect(records.items)         # the dominant entry point (LIVE)
+            # every entry point, in one extra untimed pass (full bracketing would perturb the timed region)
+            extra = Recorder()
+            sched.live_pass(sp_, extra, extra)
+            if shadows_opt:
+                run_shadows(lib, wl, sp_, range(L), extra)
+            torch.cuda.synchronize()
+            tot_x, cnt_x, byt_x, per_shape_x = collect(extra.items)
+            # the forward alone, replayed as a hipGraph of its own against the same launches live: HIP events around whole passes, no
+            # profiler (profiles/README.md: do the 8-25 us gaps rocprofv3 shows in front of the forward kernels of a graph replay exist?)
+            fwd_only = None
+            if args.probe_forward and args.chains == 1:
+                try:
+                    pst = torch.cuda.Stream(device=dev, priority=-1 if args.chain_priority == "high" else 0)
+                    with torch.cuda.stream(pst):
+                        run_forward(lib, wl, c_void_p(pst.cuda_stream), shadows=shadows_main)
+                    torch.cuda.synchronize()
+                    fg = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(fg, stream=pst):
+                        run_forward(lib, wl, c_void_p(torch.cuda.current_stream().cuda_stream), shadows=shadows_main)
+                    torch.cuda.synchronize()
+
+                    def _timed(fn, n=6):
+                        fn()
+                        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        a.record()
+                        for _ in range(n):
+                            fn()
+                        b.record()
+                        torch.cuda.synchronize()
+                        return a.elapsed_time(b) / n
+                    g_ms = _timed(fg.replay)
+                    l_ms = _timed(lambda: run_forward(lib, wl, sp_, None, shadows=shadows_main))
+                    fwd_only = {"graph_ms": round(g_ms, 3), "live_ms": round(l_ms, 3), "launches": sum(2 if u.fused else 3 for u in units_all),
+                                "what": "forward pass alone, 6 passes between two HIP events: replay of a forward-only hipGraph vs the same launches live"}
+                    del fg
+                except Exception as exc:                 # a probe, never a requirement
+                    fwd_only = {"error": repr(exc)}
+            live_items = records.items
+            table = {}
+            for (n, label, di, dos), (ms, c_, nb) in sorted(per_shape_x.items()):
+                avg = ms / c_
+                table[f"{n}[{label}: {di}->{'/'.join(str(v) for v in dos)}]"] = {"avg_ms": round(avg, 4), "algo_GBps": round(nb / (avg * 1e-3) / 1e9, 1)}
+            # the dominant kernel: the largest entry point of a pass that is ONE kernel launch
+            # (moka_up_fwd -> moka_yt_kernel<RP> for the batched launches, moka_expand_kernel<.., true> for single projections; grouped units
+            #  run their members in one launch, grid z)
+            # the dominant KERNEL: every launch of moka_up_fwd is moka_yx_kernel<RP> where the whole stack runs the fused forward (the headline);
+            # otherwise the entry point is served by several kernels and the line names them
+            RPk = _lib.rank_pad(args.rank)
+            all_fused = all(u.fused for u in units_all)
+            any_fused = any(u.fused for u in units_all)
+            kern_name = ("moka_yx_kernel<%d>" % RPk) if all_fused else (
+                ("moka_yx_kernel<%d> (units %s) + " % (RPk, ", ".join(sorted({u.label for u in units_all if u.fused}))) if any_fused else "") +
+                "moka_yt_kernel<%d> / moka_expand_kernel<%d,NQ,true> (three-launch units)" % (RPk, RPk))
+            dom = "moka_up_fwd"
+            dom_bytes = byt[dom]
+            dom_avg_ms = tot[dom] / cnt[dom]
+            achieved = dom_bytes / cnt[dom] / (dom_avg_ms * 1e-3) / 1e9
+            traffic, traffic_src = None, None
+            if not args.no_traffic and (args.model, args.rank, args.variant) == ("7b", 16, "avt") and not args.no_group:
+                # (the PMC passes profile the headline workload; per launch = per layer / the layer's up-projection launches)
+                traffic, traffic_src = pmc_traffic_per_launch(T, wl["units_per_layer"])
+                if traffic is not None:
+                    traffic = round(traffic / args.chains)   # (the PMC passes profile whole-batch launches; traffic is linear in the tokens)
+                if args.chains > 1 and traffic is not None:
+                    traffic_src += " / %d (launches of %d tokens)" % (args.chains, T // args.chains)
+                elif traffic is not None:
+                    traffic_src += " (measured on launches of %d tokens, scaled)" % json.load(open(PMC_TRAFFIC_FILE))["tokens"]
+            out.update({
+                "graph_replay_host_ms": replay_host_ms,
+                "roofline": {"bound": "hbm", "kernel": kern_name, "entry_point": "moka_up_fwd_fused" if all_fused else "moka_up_fwd",
+                             "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
+                             "algorithmic_bytes_per_launch": round(dom_bytes / cnt[dom]),
+                             "avg_launch_ms": round(dom_avg_ms, 4), "launches_timed": cnt[dom],
+                             "where": ("live passes right behind the timed region (the timed region replays a hipGraph: nothing can be bracketed inside it)"
+                                       if roof_behind else "HIP events inside the timed region (every %d-th launch)" % args.bracket_every),
+                             "note": (None if args.chains == 1 else
+                                      "launches of %d tokens timed ALONE, the %d chains back to back on one stream; in the step they run beside the other chain's "
+                                      "launches (not observable inside a graph; rocprofv3 serialises the dispatches) -- adapter_hbm_roofline_frac is the step's figure"
+                                      % (T // args.chains, args.chains)),
+                             # the dominant family INSIDE the timed schedule (both chains, hub launches and all): marginal of leaving its launches out
+                             "in_schedule": (dict(kernel=kern_name, family="up_fwd", **ablation["families"]["up_fwd"], how=ablation["how"])
+                                             if (ablation and "up_fwd" in ablation["families"]) else None)},
+                "entry_point_ms_per_pass": {n: round(tot_x[n], 3) for n in ENTRY},
+                "forward_only": fwd_only,
+                "kernels": table,
+            })
+            if ablation is not None and args.ablate != "dominant":
+                out["ablation"] = ablation
         if world == 1 and args.e2e:
             del wl, opt, records
             torch.cuda.empty_cache()
             out["end_to_end"] = end_to_end(args, dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args)
         final_line = json.dumps(out)
     if world > 1:

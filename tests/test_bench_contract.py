@@ -83,3 +83,35 @@ def test_a_missing_traffic_summary_does_not_kill_the_line(monkeypatch, capsys):
     t, src = bench.pmc_traffic_per_launch(8192, 4)
     assert t is None and src.startswith("missing: ")
     assert "is missing" in capsys.readouterr().err
+
+
+def test_a_plain_run_measures_the_headline_only():
+    """`bench.py --gpus 1 --steps N --warmup W` times the steps and prints the line; what takes runs of its own is behind --full, which the
+    opt-in probes imply (they read what it measures)."""
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert not a.full and a.ablate == "off" and a.steps == 7 and a.warmup == 3 and a.dump_outputs is None
+    a = bench.parse_args(["--full"])
+    assert a.full and a.ablate == "dominant"
+    for extra in (["--verify-graph"], ["--probe-forward"], ["--e2e"], ["--ablate", "all"]):
+        assert bench.parse_args(extra).full, extra
+    a = bench.parse_args(["--full", "--ablate", "off", "--dump-outputs", "out"])
+    assert a.full and a.ablate == "off" and a.dump_outputs == "out"
+
+
+def test_dump_outputs_is_float32_bounded_and_repeatable(tmp_path):
+    import numpy as np
+    g = torch.Generator().manual_seed(3)
+    small = torch.randn(5, 7, generator=g).to(torch.bfloat16)
+    big = torch.randn(3000, 1000, generator=g)
+    outs = [("y.small", small), ("params", big)]
+    budget = 1 << 20                                       # 262144 float32 in all: 131072 per output
+    n = bench.dump_outputs(outs, str(tmp_path / "a"), budget=budget)
+    assert n <= budget
+    ys = np.load(tmp_path / "a" / "y.small.npy")
+    assert ys.dtype == np.float32 and np.array_equal(ys, small.float().reshape(-1).numpy())       # small enough: all of it, in order
+    ps = np.load(tmp_path / "a" / "params.npy")
+    assert ps.dtype == np.float32 and ps.size == budget // 4 // 2
+    assert np.isin(ps, big.reshape(-1).numpy()).all()                                           # a sample of the output's own elements
+    bench.dump_outputs(outs, str(tmp_path / "b"), budget=budget)
+    assert np.array_equal(ps, np.load(tmp_path / "b" / "params.npy"))                            # the same elements every time
+    assert bench.DUMP_BYTES + 128 * 1000 <= 64 * 10 ** 6                                            # headers of 1000 outputs included

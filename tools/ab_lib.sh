@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage: ab_lib.sh "<bench args>" lib1.so lib2.so ...   ("default" = the in-tree build): entry-point split per library
-BARGS=$1; shift
+BARGS="--full $1"; shift          # (reads entry_point_ms_per_pass: a --full figure)
 mkdir -p gpurun_out/ab; rm -f gpurun_out/ab/ablib.log
 for l in "$@"; do
   if [ "$l" = "default" ]; then unset MOKA_HIP_LIB; else export MOKA_HIP_LIB=$PWD/$l; fi

@@ -2,7 +2,7 @@
 # usage: ab_tune.sh "<bench args>" tune1 tune2 ...   ("none" = defaults): entry-point split of bench.py per MOKA_TUNE string
 # moka_tune lives in the diagnostics build only (the product library keeps no mutable state)
 export MOKA_HIP_LIB=${MOKA_HIP_LIB:-$PWD/moka_amd/libmoka_hip_diag.so}
-BARGS=$1; shift
+BARGS="--full $1"; shift          # (reads entry_point_ms_per_pass: a --full figure)
 mkdir -p gpurun_out/ab; rm -f gpurun_out/ab/abtune.log
 for t in "$@"; do
   if [ "$t" = "none" ]; then tt=""; else tt=$t; fi

@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: ab_units.sh "<bench args>" <entry point> tune1 tune2 ...   ("none" = defaults): per-unit avg_ms of one entry point per MOKA_TUNE string
 export MOKA_HIP_LIB=${MOKA_HIP_LIB:-$PWD/moka_amd/libmoka_hip_diag.so}
-BARGS=$1; EP=$2; shift; shift
+BARGS="--full $1"; EP=$2; shift; shift          # (reads `kernels`: a --full figure)
 for t in "$@"; do
   if [ "$t" = "none" ]; then tt=""; else tt=$t; fi
   MOKA_TUNE=$tt python bench.py --steps 10 --no-cpu-baseline --no-traffic $BARGS 2>/dev/null | python -c "

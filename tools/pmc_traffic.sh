@@ -7,7 +7,7 @@ mkdir -p $OUT
 LAYERS=4
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/pmcF /tmp/pmcW /tmp/pmc[0-9]*
-# --graph off --steps 1 --warmup 1: 2 optimizer steps + the extra bracketed passes; every pass runs the forward once per layer
+# --graph off --steps 1 --warmup 1: 2 optimizer steps (a plain run: no bracketed passes behind them); every pass runs the forward once per layer
 # --batch 2: the default schedule runs the micro-batch of 4 sequences as two part-batch chains, i.e. launches of 4096 tokens (the launch
 # heuristics follow T: the fused up-projection uses 8 column ranges per token block there, 4 at 8192 tokens)
 timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d /tmp/pmcF -o f -- python $REPO/bench.py --layers $LAYERS --steps 1 --warmup 1 --graph off --batch 2 --no-cpu-baseline --no-traffic > $OUT/runF.log 2>&1

@@ -1,6 +1,6 @@
 #!/bin/bash
 # rocprofv3 kernel trace of bench.py on the GPU box -> gpurun_out/<tag>/{kernel_trace.md,timeline.md}.  usage: prof_run.sh <tag> [bench args]
-TAG=$1; shift
+TAG=$1; shift; set -- --full "$@"          # (the timelines below leave out the live passes --full runs behind the timed region)
 REPO=$PWD
 mkdir -p gpurun_out/$TAG
 cd /tmp && export TMPDIR=/tmp

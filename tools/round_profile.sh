@@ -4,7 +4,7 @@ TAG=${1:-r06}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 N="--no-cpu-baseline --no-traffic"
-b() { name=$1; shift; timeout 900 python bench.py "$@" > $OUT/$name.json 2>> $OUT/bench.err; }
+b() { name=$1; shift; timeout 900 python bench.py --full "$@" > $OUT/$name.json 2>> $OUT/bench.err; }
 b bench                                                        # the default command: 120 steps, cpu_baseline, traffic (2 part-batch chains, hub-shaped graph)
 b bench_driver_command --steps 20 --warmup 5 $N                # what the driver runs (--steps 20 --warmup 5)
 b bench_chains1 --steps 60 --chains 1 $N                       # one chain: round 4's graph shape with the chain-first capture order

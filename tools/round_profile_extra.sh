@@ -3,7 +3,7 @@
 TAG=${1:-r06}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
-N="--no-cpu-baseline --no-traffic"
+N="--full --no-cpu-baseline --no-traffic"
 python bench.py --model 13b --rank 64 --seq 4096 --batch 2 --steps 10 $N > $OUT/bench_13b_r64_seq4096.json 2>> $OUT/bench.err
 python bench.py --model 13b --rank 64 --seq 4096 --batch 2 --steps 10 --chains 2 $N > $OUT/bench_13b_r64_seq4096_chains2.json 2>> $OUT/bench.err
 python bench.py --model 70b --steps 6 $N > $OUT/bench_70b.json 2>> $OUT/bench.err
