@@ -38,7 +38,8 @@ class Case:
     big: bool = False                 # store strided samples instead of full tensors
 
 # layout kinds:  p = padding (no modality), t = text, v = video/image, a = audio,
-#                q = question text (text AND question), Q = question token that is NOT text
+#                q = question text (text AND question), Q = question token that is NOT text,
+#                I = image/video token inside the question set (VT: a query row that is also a key row)
 
 
 def _avt_tiny(**kw):
@@ -108,6 +109,8 @@ _CASES: Dict[str, dict] = {
                                         [("v", 32), ("q", 1), ("t", 15)]]),
     "vt_nontext_question": _vt_tiny(seed=37, layouts=[[("t", 6), ("v", 16), ("q", 4), ("Q", 3), ("q", 2), ("t", 12), ("p", 5)],
                                                       [("t", 2), ("v", 16), ("q", 14), ("t", 16)]]),
+    "vt_image_question": _vt_tiny(seed=42, w=1.0, layouts=[[("t", 6), ("v", 12), ("q", 4), ("I", 3), ("q", 3), ("v", 4), ("t", 11), ("p", 5)],
+                                                           [("t", 2), ("I", 2), ("v", 8), ("q", 5), ("I", 4), ("q", 6), ("t", 21)]]),
     "vt_none": dict(variant="vt", B=2, S=5, d_in=64, d_out=96, r=8, alpha=16.0, w=0.05, masks_none=True,
                     layouts=[[("t", 5)]] * 2, seed=38),
     "vt_cfg1_q": dict(variant="vt", B=1, S=256, d_in=4096, d_out=4096, r=8, alpha=16.0, w=0.05, seed=39, big=True,
@@ -169,6 +172,9 @@ def build_layout(layout: List[Tuple[str, int]], S: int, gap_question: bool = Fal
             question[sl] = True
         elif kind == "Q":
             question[sl] = True       # question token that belongs to no modality
+        elif kind == "I":
+            tok_mod[sl] = VIS
+            question[sl] = True       # image token inside the question set
         elif kind != "p":
             raise ValueError(kind)
         pos += n

@@ -153,12 +153,19 @@ def sample_idx(n, k):
     return np.unique(np.round(np.linspace(0, n - 1, k)).astype(np.int64))
 
 
-def main():
+def main(only=None):
+    """only: names of the cases to (re)generate; the log keeps the entries of every other case as they are."""
     torch.manual_seed(0)
     AvtLinear, VtLinear = _import_reference()
     os.makedirs(OUT, exist_ok=True)
     log = []
-    for name in C.case_names():
+    names = C.case_names()
+    if only:
+        unknown = sorted(set(only) - set(names))
+        if unknown:
+            raise SystemExit(f"unknown cases: {unknown}")
+        names = [n for n in names if n in only]
+    for name in names:
         c = C.get_case(name)
         cd = C.make_case_data(name)
         build = build_avt if c.variant == "avt" else build_vt
@@ -227,11 +234,23 @@ def main():
         np.savez_compressed(os.path.join(OUT, name + ".npz"), **out)
         log.append(entry)
         print(json.dumps(entry))
-    with open(os.path.join(OUT, "GENERATION_LOG.json"), "w") as f:
-        json.dump({"torch": torch.__version__, "entries": log}, f, indent=1)
+    log_path = os.path.join(OUT, "GENERATION_LOG.json")
+    if only:
+        with open(log_path) as f:
+            prev = json.load(f)
+        fresh = {e["case"]: e for e in log}
+        kept = [fresh.pop(e["case"], e) for e in prev["entries"]]
+        order = {n: i for i, n in enumerate(C.case_names())}
+        log = sorted(kept + list(fresh.values()), key=lambda e: order.get(e["case"], len(order)))
+        version = prev["torch"]
+    else:
+        version = torch.__version__
+    with open(log_path, "w") as f:
+        json.dump({"torch": version, "entries": log}, f, indent=1)
     tot = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT))
     print(f"wrote {len(log)} cases, {tot/1e6:.2f} MB total")
 
 
 if __name__ == "__main__":
-    main()
+    # python oracle/make_goldens.py [CASE ...]: only the named cases (default: all)
+    main(sys.argv[1:] or None)

@@ -143,6 +143,64 @@ class Ctx:
     probs: List[Optional[torch.Tensor]] = field(default_factory=list)
 
 
+@dataclass
+class Interaction:
+    """The rank-space interaction of one forward: h [B,S,r] (pre-update rows), hp [B,S,r] and the softmax P [nq_b, Lk_b] of
+    every sample (None: no query row or no key)."""
+    h: torch.Tensor
+    hp: torch.Tensor
+    P: List[Optional[torch.Tensor]]
+    routing: Routing
+    w: float
+    inv_sqrt_dk: float
+
+
+def interaction_forward(h: torch.Tensor, routing: Routing, w: float, inv_sqrt_dk: float) -> Interaction:
+    """hp[t] = h[t] + w * softmax(h[t] K_b^T * inv_sqrt_dk) K_b on the query rows t of sample b, hp = h elsewhere.
+    K_b = rows kpos_b of h, zeroed where not kvalid (keys == values, taken before the update).  Arithmetic in h's dtype."""
+    hp = h.clone()
+    probs: List[Optional[torch.Tensor]] = []
+    c = inv_sqrt_dk
+    for b in range(h.shape[0]):
+        kp = routing.kpos[b]
+        qrows = torch.where(routing.is_query[b])[0]
+        if kp.numel() == 0 or qrows.numel() == 0:
+            probs.append(None)
+            continue
+        K = h[b, kp] * routing.kvalid[b].to(h.dtype).unsqueeze(-1)
+        P = torch.softmax((h[b, qrows] @ K.t()) * c, dim=-1)
+        hp[b, qrows] = h[b, qrows] + w * (P @ K)
+        probs.append(P)
+    return Interaction(h, hp, probs, routing, w, c)
+
+
+def interaction_backward(g: torch.Tensor, ia: Interaction) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """g = dL/dhp [B,S,r] -> (dh, dq, dkey), dh = g + dq + dkey.  dq [B,S,r]: the query part (non-zero on query rows only);
+    dkey [B,S,r]: the key part, value role + key role, summed into the key's row (non-zero on valid key rows only).  A row that
+    is both a query and a key row (VT masks may overlap) gets both parts."""
+    rt = ia.routing
+    dtype = g.dtype
+    dq_all = torch.zeros_like(g)
+    dk_all = torch.zeros_like(g)
+    c = ia.inv_sqrt_dk
+    for b in range(g.shape[0]):
+        P = ia.P[b]
+        if P is None:
+            continue
+        kp, kv = rt.kpos[b], rt.kvalid[b].to(dtype).unsqueeze(-1)
+        qrows = torch.where(rt.is_query[b])[0]
+        K = ia.h[b, kp] * kv
+        q = ia.h[b, qrows]
+        do = ia.w * g[b, qrows]                         # dL/d(P K)
+        dP = do @ K.t()
+        dS = P * (dP - (P * dP).sum(-1, keepdim=True))  # softmax backward
+        dq = c * (dS @ K)
+        dK = P.t() @ do + c * (dS.t() @ q)              # value role + key role
+        dq_all[b, qrows] += dq
+        dk_all[b].index_add_(0, kp, dK * kv)
+    return g + dq_all + dk_all, dq_all, dk_all
+
+
 def adapter_forward(x: torch.Tensor, y0: torch.Tensor, A: Sequence[torch.Tensor], Bw: torch.Tensor,
                     routing: Routing, s_in: float, s_out: Sequence[float], w: float, d_k: int,
                     dtype: torch.dtype = torch.float64) -> Tuple[torch.Tensor, Ctx]:
@@ -161,19 +219,8 @@ def adapter_forward(x: torch.Tensor, y0: torch.Tensor, A: Sequence[torch.Tensor]
         sel = routing.tok_mod == m
         if sel.any():
             h[sel] = s_in * (x[sel] @ A[m].t())
-    hp = h.clone()
-    probs: List[Optional[torch.Tensor]] = []
-    c = 1.0 / math.sqrt(d_k)
-    for b in range(Bsz):
-        kp = routing.kpos[b]
-        qrows = torch.where(routing.is_query[b])[0]
-        if kp.numel() == 0 or qrows.numel() == 0:
-            probs.append(None)
-            continue
-        K = h[b, kp] * routing.kvalid[b].to(dtype).unsqueeze(-1)
-        P = torch.softmax((h[b, qrows] @ K.t()) * c, dim=-1)
-        hp[b, qrows] = h[b, qrows] + w * (P @ K)
-        probs.append(P)
+    ia = interaction_forward(h, routing, w, 1.0 / math.sqrt(d_k))
+    hp, probs = ia.hp, ia.P
     scale = torch.zeros(Bsz, S, 1, dtype=dtype)
     for m in range(routing.n_mod):
         scale[routing.tok_mod == m] = s_out[m]
@@ -196,23 +243,8 @@ def adapter_backward(gy: torch.Tensor, ctx: Ctx):
     gs = gy * scale                                     # [B,S,d_out]
     dB = torch.einsum("bso,bsk->ok", gs, ctx.hp)        # [d_out, r]
     ghp = gs @ ctx.Bw                                   # dL/dh'  [B,S,r]
-    dh = ghp.clone()
-    c = 1.0 / math.sqrt(ctx.d_k)
-    for b in range(Bsz):
-        P = ctx.probs[b]
-        if P is None:
-            continue
-        kp, kv = rt.kpos[b], rt.kvalid[b].to(dtype).unsqueeze(-1)
-        qrows = torch.where(rt.is_query[b])[0]
-        K = ctx.h[b, kp] * kv
-        q = ctx.h[b, qrows]
-        do = ctx.w * ghp[b, qrows]                      # dL/d(P K)
-        dP = do @ K.t()
-        dS = P * (dP - (P * dP).sum(-1, keepdim=True))  # softmax backward
-        dq = c * (dS @ K)
-        dK = P.t() @ do + c * (dS.t() @ q)              # value role + key role
-        dh[b, qrows] += dq
-        dh[b].index_add_(0, kp, dK * kv)
+    ia = Interaction(ctx.h, ctx.hp, ctx.probs, rt, ctx.w, 1.0 / math.sqrt(ctx.d_k))
+    dh, _, _ = interaction_backward(ghp, ia)
     dA = []
     dx = torch.zeros_like(ctx.x)
     for m in range(rt.n_mod):
