@@ -44,6 +44,25 @@
  *     (fp32 [d_out, r]);   moka_down_bwd: `dh_tok` = s_in * dh  fp32 [T, RP] (0 for tokens of no modality), `dh_kmj` unused,
  *     `AT` = the A_m stacked, fp32 [M, r, d_in].  moka_cross_fwd / moka_cross_bwd are storage independent (pass hp / dh, which
  *     are optional for bf16, and NULL for the weight shadows).  Groups run one projection at a time.
+ *   - pointer alignment.  Every entry point checks the DEVICE pointers it is handed before its first launch: a pointer off its
+ *     requirement gives MOKA_EINVAL ("... must be N-byte aligned" in moka_last_error()) and nothing has been launched or written.
+ *     Feature widths are multiples of 32 elements and rank pads multiples of 16, so an aligned base keeps every row aligned.
+ *       16 bytes  x, gy, y_inout, dx_inout, A_m, Bw, BwT, AT, the *_tok and *_kmj packs (elements of host pointer arrays included):
+ *                 each lane reads or writes them 8 bf16 at a time (global_load_dwordx4 / global_store_dwordx4); x and gy also travel
+ *                 by LDS-DMA (global_load_lds_dwordx4), whose per-lane source address has to be 16-byte aligned; Bw rows are read
+ *                 as one 16-byte vector when r == RP.
+ *       16 bytes  part, g_part, h, hp, dh (fp32 rank space: rows are summed and stored four floats at a time), the moka_cross_bwd
+ *                 workspace `ws`, and tok_mod (read 16 ids per lane by the expand kernels; moka_routing.tok_mod likewise).
+ *       16 bytes  the same arguments under MOKA_F32.  The fp32 kernels themselves move single dwords (global_load_dword /
+ *                 global_store_dword) and would be served by 4 bytes; the rule is kept the same for both storage types because the
+ *                 rank-space kernels in between are shared.
+ *        4 bytes  dA_acc, dB_acc: never touched by a vector access -- the weight-gradient kernels add one dword per (column, rank)
+ *                 with global_atomic_add_f32, the deterministic mode's second stage (moka_sum_runs_kernel) is a dword
+ *                 read-modify-write per element -- so a [rows, cols] view at ANY element offset of a flat fp32 gradient buffer is valid.
+ *        4 bytes  moka_routing.ktok / klen / kslot (dword loads; not checked beyond what int32_t* implies).
+ *        none     keep_out of moka_dropout_mask (byte stores).
+ *     moka_opts.det_ws: 16, moka_opts.seed_dev: 8, the AdamW buffers: stated with those entry points.  Host arrays (pointer lists,
+ *     s_out, d_out, seeds): the natural alignment of their element type.
  *
  * Unified routed formulation (oracle/moka_oracle.py):
  *     h[t]  = s_in * x[t] A[mod(t)]^T                 (0 when mod(t) == MOKA_MOD_NONE)

@@ -48,6 +48,14 @@ static int check_det_opts(const char* fn, const moka_opts* o_in, bool wants_wgra
     return MOKA_OK;
 }
 
+// ---- pointer alignment (include/moka_hip.h, "pointer alignment"): checked by every entry point BEFORE its first launch, so a refused call has
+// written nothing.  NULL passes (optional arguments; the required ones have their own null checks).  16: operands the kernels touch 16 bytes
+// per lane (vector loads / stores, LDS-DMA); 4: the fp32 accumulators (one dword atomic or dword read-modify-write per element).
+#define NEED_ALIGNED(fn, what, p, bytes) do { if ((uintptr_t)(p) & ((bytes) - 1)) \
+    return fail(MOKA_EINVAL, "%s: %s must be %d-byte aligned (include/moka_hip.h: pointer alignment)", fn, what, (int)(bytes)); } while (0)
+#define NEED16(fn, what, p) NEED_ALIGNED(fn, what, p, 16)
+#define NEED4(fn, what, p) NEED_ALIGNED(fn, what, p, 4)
+
 extern "C" {
 
 int moka_version(void) { return MOKA_VERSION; }
@@ -145,6 +153,12 @@ int moka_down_fwd_group(const void* x, const void* const* A, const uint8_t* tok_
     if (G < 1 || G > MOKA_MAX_GROUP) return fail(MOKA_EINVAL, "moka_down_fwd: G=%d not in 1..%d", G, MOKA_MAX_GROUP);
     if (!x || !A || !tok_mod || !part) return fail(MOKA_EINVAL, "moka_down_fwd: null pointer");
     if (dropout_p != 0.f && !seeds) return fail(MOKA_EINVAL, "moka_down_fwd: dropout without seeds");
+    NEED16("moka_down_fwd", "x", x);
+    NEED16("moka_down_fwd", "tok_mod", tok_mod);
+    for (int g = 0; g < G; ++g) {
+        NEED16("moka_down_fwd", "part", part[g]);
+        for (int m = 0; m < M; ++m) NEED16("moka_down_fwd", "A", A[g * M + m]);
+    }
     DropArgs drop[MOKA_MAX_GROUP];
     float inv_keep = 1.f;
     for (int g = 0; g < G; ++g) {
@@ -212,26 +226,36 @@ int moka_cross_fwd_group(const float* const* part, int ks, const moka_routing* r
     for (int g = 0; g < G; ++g) {
         CrossArgs& a = ab.z[g];
         if (!part[g] || !h[g] || !hp_kmj[g]) return fail(MOKA_EINVAL, "moka_cross_fwd: null pointer (projection %d)", g);
+        NEED16("moka_cross_fwd", "part", part[g]);
+        NEED16("moka_cross_fwd", "h", h[g]);
+        NEED16("moka_cross_fwd", "hp", hp ? hp[g] : nullptr);
+        NEED16("moka_cross_fwd", "hp_tok", hp_tok ? hp_tok[g] : nullptr);
+        NEED16("moka_cross_fwd", "hp_kmj", hp_kmj[g]);
         a.part = part[g]; a.ks = ks; a.out_f32 = h[g]; a.out_f32b = hp ? hp[g] : nullptr;
         a.pack_tok = hp_tok ? (unsigned short*)hp_tok[g] : nullptr;     // (optional: moka_up_fwd_fused does not read it)
         a.pack_kmj = (unsigned short*)hp_kmj[g];
         if (BwT && BwT[g]) {
             if (!Bw || !Bw[g] || !d_out || d_out[g] < 32) return fail(MOKA_EINVAL, "moka_cross_fwd: BwT requested without Bw / d_out");
+            NEED16("moka_cross_fwd", "Bw", Bw[g]);
+            NEED16("moka_cross_fwd", "BwT", BwT[g]);
             a.Bw = (const unsigned short*)Bw[g]; a.BwT = (unsigned short*)BwT[g]; a.C = d_out[g];
         }
         if (AT && AT[g]) {
             if (!A || d_in < 32) return fail(MOKA_EINVAL, "moka_cross_fwd: AT requested without A / d_in");
+            NEED16("moka_cross_fwd", "AT", AT[g]);
             a.AT = (unsigned short*)AT[g]; a.Cin = d_in;
         }
         for (int m = 0; m < rt->M && m < MOKA_MAX_MOD; ++m) {
             a.s_mod[m] = s_out[m];
             if (a.AT) {
                 if (!A[g * rt->M + m]) return fail(MOKA_EINVAL, "moka_cross_fwd: A[%d] is null", g * rt->M + m);
+                NEED16("moka_cross_fwd", "A", A[g * rt->M + m]);
                 a.Aw[m] = (const unsigned short*)A[g * rt->M + m];
             }
         }
         a.w = w; a.c = inv_sqrt_dk;
     }
+    NEED16("moka_cross_fwd", "moka_routing.tok_mod", rt->tok_mod);
     return mk_launch_cross(false, ab, G, rt, r, (hipStream_t)stream);
 }
 
@@ -267,6 +291,12 @@ int moka_cross_bwd_group(const float* const* g_part, int ks, const float* const*
     for (int g = 0; g < G; ++g) {
         CrossArgs& a = ab.z[g];
         if (!g_part[g] || !h[g] || !dh_tok[g] || !dh_kmj[g] || !ws[g]) return fail(MOKA_EINVAL, "moka_cross_bwd: null pointer (projection %d)", g);
+        NEED16("moka_cross_bwd", "g_part", g_part[g]);
+        NEED16("moka_cross_bwd", "h", h[g]);
+        NEED16("moka_cross_bwd", "dh", dh ? dh[g] : nullptr);
+        NEED16("moka_cross_bwd", "dh_tok", dh_tok[g]);
+        NEED16("moka_cross_bwd", "dh_kmj", dh_kmj[g]);
+        NEED16("moka_cross_bwd", "ws", ws[g]);
         for (int g2 = 0; g2 < g; ++g2)
             if (ws[g2] == ws[g]) return fail(MOKA_EINVAL, "moka_cross_bwd: projections %d and %d share one workspace", g2, g);
         const size_t nblk8 = (size_t)(rt->S + 7) / 8;
@@ -277,6 +307,7 @@ int moka_cross_bwd_group(const float* const* g_part, int ks, const float* const*
         for (int m = 0; m < MOKA_MAX_MOD; ++m) a.s_mod[m] = s_in;
         a.w = w; a.c = inv_sqrt_dk;
     }
+    NEED16("moka_cross_bwd", "moka_routing.tok_mod", rt->tok_mod);
     return mk_launch_cross(true, ab, G, rt, r, (hipStream_t)stream);
 }
 
@@ -293,6 +324,12 @@ int moka_up_fwd_group(const void* const* hp_tok, const void* const* Bw, const ui
                       int T, int r, const int* d_out, int G, int dtype, moka_stream_t stream) {
     GROUP_CHECK("moka_up_fwd");
     if (!hp_tok || !Bw || !tok_mod || !y_inout || !d_out) return fail(MOKA_EINVAL, "moka_up_fwd: null pointer");
+    NEED16("moka_up_fwd", "tok_mod", tok_mod);
+    for (int g = 0; g < G; ++g) {                        // (all projections before the first launch: fp32 storage launches one at a time)
+        NEED16("moka_up_fwd", "hp_tok", hp_tok[g]);
+        NEED16("moka_up_fwd", "Bw", Bw[g]);
+        NEED16("moka_up_fwd", "y_inout", y_inout[g]);
+    }
     ExpandBatch ab;
     memset(&ab, 0, sizeof(ab));
     for (int g = 0; g < G; ++g) {
@@ -362,11 +399,14 @@ int moka_up_fwd_fused_group(const float* const* part, int ks, const moka_routing
         if (rc) return rc;
         if (!part[g] || !Bw[g] || !y_inout[g]) return fail(MOKA_EINVAL, "moka_up_fwd_fused: null pointer (projection %d)", g);
         if ((uintptr_t)part[g] & 15) return fail(MOKA_EINVAL, "moka_up_fwd_fused: part must be 16-byte aligned");
+        NEED16("moka_up_fwd_fused", "Bw", Bw[g]);
+        NEED16("moka_up_fwd_fused", "y_inout", y_inout[g]);
         fb.z[g].part = part[g]; fb.z[g].Bw = (const unsigned char*)Bw[g]; fb.z[g].out = (unsigned char*)y_inout[g]; fb.z[g].C = d_out[g];
         fb.z[g].h_out = h ? h[g] : nullptr;
         fb.z[g].kmj_out = hp_kmj ? (unsigned short*)hp_kmj[g] : nullptr;
         if (((uintptr_t)fb.z[g].h_out | (uintptr_t)fb.z[g].kmj_out) & 15) return fail(MOKA_EINVAL, "moka_up_fwd_fused: h / hp_kmj must be 16-byte aligned");
     }
+    NEED16("moka_up_fwd_fused", "moka_routing.tok_mod", rt->tok_mod);
     fb.Tp = (T + 31) / 32 * 32;
     fb.tok_mod = rt->tok_mod; fb.ktok = rt->ktok; fb.klen = rt->klen;
     for (int m = 0; m < rt->M; ++m) fb.s_mod[m] = s_out[m];
@@ -403,14 +443,18 @@ int moka_weight_shadows_group(const void* const* Bw, const int* d_out, const voi
         a.r = r; a.M = M;
         if (BwT && BwT[g]) {
             if (!Bw || !Bw[g] || !d_out || d_out[g] < 32 || (d_out[g] % 32)) return fail(MOKA_EINVAL, "moka_weight_shadows: BwT requested without Bw / d_out");
+            NEED16("moka_weight_shadows", "Bw", Bw[g]);
+            NEED16("moka_weight_shadows", "BwT", BwT[g]);
             a.Bw = (const unsigned short*)Bw[g]; a.BwT = (unsigned short*)BwT[g]; a.C = d_out[g];
             items = a.C > items ? a.C : items;
         }
         if (AT && AT[g]) {
             if (!A || d_in < 32 || (d_in % 32)) return fail(MOKA_EINVAL, "moka_weight_shadows: AT requested without A / d_in");
+            NEED16("moka_weight_shadows", "AT", AT[g]);
             a.AT = (unsigned short*)AT[g]; a.Cin = d_in;
             for (int m = 0; m < M; ++m) {
                 if (!A[g * M + m]) return fail(MOKA_EINVAL, "moka_weight_shadows: A[%d] is null", g * M + m);
+                NEED16("moka_weight_shadows", "A", A[g * M + m]);
                 a.Aw[m] = (const unsigned short*)A[g * M + m];
             }
             items = (long)M * d_in > items ? (long)M * d_in : items;
@@ -438,14 +482,18 @@ int moka_weight_shadows_batch(const void* const* Bw, const int* d_out, const voi
         ShadowArgs& a = sb.z[i];
         if (BwT && BwT[i]) {
             if (!Bw || !Bw[i] || !d_out || d_out[i] < 32 || (d_out[i] % 32)) return fail(MOKA_EINVAL, "moka_weight_shadows_batch: BwT requested without Bw / d_out");
+            NEED16("moka_weight_shadows_batch", "Bw", Bw[i]);
+            NEED16("moka_weight_shadows_batch", "BwT", BwT[i]);
             a.Bw = (const unsigned short*)Bw[i]; a.BwT = (unsigned short*)BwT[i]; a.C = d_out[i];
             items = a.C > items ? a.C : items;
         }
         if (AT && AT[i]) {
             if (!A || !d_in || d_in[i] < 32 || (d_in[i] % 32)) return fail(MOKA_EINVAL, "moka_weight_shadows_batch: AT requested without A / d_in");
+            NEED16("moka_weight_shadows_batch", "AT", AT[i]);
             a.AT = (unsigned short*)AT[i]; a.Cin = d_in[i];
             for (int m = 0; m < M; ++m) {
                 if (!A[i * M + m]) return fail(MOKA_EINVAL, "moka_weight_shadows_batch: A[%d] is null", i * M + m);
+                NEED16("moka_weight_shadows_batch", "A", A[i * M + m]);
                 a.Aw[m] = (const unsigned short*)A[i * M + m];
             }
             items = (long)M * d_in[i] > items ? (long)M * d_in[i] : items;
@@ -466,6 +514,7 @@ int moka_up_bwd_group(const void* const* gy, const void* const* hp_kmj, const vo
                       int T, int r, const int* d_out, int M, int G, int dtype, const moka_opts* opts, moka_stream_t stream) {
     GROUP_CHECK("moka_up_bwd");
     if (!gy || !tok_mod || !s_out || !d_out) return fail(MOKA_EINVAL, "moka_up_bwd: null pointer");
+    NEED16("moka_up_bwd", "tok_mod", tok_mod);
     const int RP = rank_pad(r);
     DetScope det_scope(opts);
     int Cmax = 0;
@@ -473,6 +522,11 @@ int moka_up_bwd_group(const void* const* gy, const void* const* hp_kmj, const vo
         int rc = check_common("moka_up_bwd", T, d_out[g], r, M, dtype);
         if (rc) return rc;
         if (!gy[g]) return fail(MOKA_EINVAL, "moka_up_bwd: gy[%d] is null", g);
+        NEED16("moka_up_bwd", "gy", gy[g]);
+        NEED16("moka_up_bwd", "hp_kmj", hp_kmj ? hp_kmj[g] : nullptr);
+        NEED16("moka_up_bwd", "BwT", BwT ? BwT[g] : nullptr);
+        NEED16("moka_up_bwd", "g_part", g_part ? g_part[g] : nullptr);
+        NEED4("moka_up_bwd", "dB_acc", dB_acc ? dB_acc[g] : nullptr);
         if ((g_part && !g_part[g] != !g_part[0]) || (dB_acc && !dB_acc[g] != !dB_acc[0]))
             return fail(MOKA_EINVAL, "moka_up_bwd: an output must be requested for every projection of the group or for none");
         Cmax = d_out[g] > Cmax ? d_out[g] : Cmax;
@@ -561,6 +615,12 @@ int moka_up_bwd_db_batch(const void* const* gy, const void* const* hp_kmj, const
     if (n < 1 || n > MOKA_MAX_BATCH) return fail(MOKA_EINVAL, "moka_up_bwd_db_batch: n=%d not in 1..%d", n, MOKA_MAX_BATCH);
     if (!gy || !hp_kmj || !d_out || !tok_mod || !dB_acc) return fail(MOKA_EINVAL, "moka_up_bwd_db_batch: null pointer");
     if (dtype != MOKA_BF16) return fail(MOKA_EINVAL, "moka_up_bwd_db_batch: bf16 storage only (fp32 storage: one moka_up_bwd call per projection)");
+    NEED16("moka_up_bwd_db_batch", "tok_mod", tok_mod);
+    for (int i = 0; i < n; ++i) {                        // (every problem before the first launch: the deterministic mode launches one at a time)
+        NEED16("moka_up_bwd_db_batch", "gy", gy[i]);
+        NEED16("moka_up_bwd_db_batch", "hp_kmj", hp_kmj[i]);
+        NEED4("moka_up_bwd_db_batch", "dB_acc", dB_acc[i]);
+    }
     if (int drc = check_det_opts("moka_up_bwd_db_batch", opts, false, T, 32, r, 1, M)) return drc;
     if (opts_view(opts).det_ws) {
         const float s1[MOKA_MAX_MOD] = {1.f, 1.f, 1.f};                      // (s_out is carried by the pack: unused by the dB half)
@@ -592,6 +652,15 @@ int moka_down_bwd_group(const void* const* dh_tok, const void* const* dh_kmj, co
     int rc = check_common("moka_down_bwd", T, d_in, r, M, dtype);
     if (rc) return rc;
     if (!tok_mod) return fail(MOKA_EINVAL, "moka_down_bwd: null pointer");
+    NEED16("moka_down_bwd", "tok_mod", tok_mod);
+    NEED16("moka_down_bwd", "x", x);
+    NEED16("moka_down_bwd", "dx_inout", dx_inout);
+    for (int g = 0; g < G; ++g) {
+        NEED16("moka_down_bwd", "dh_tok", dh_tok ? dh_tok[g] : nullptr);
+        NEED16("moka_down_bwd", "dh_kmj", dh_kmj ? dh_kmj[g] : nullptr);
+        NEED16("moka_down_bwd", "AT", AT ? AT[g] : nullptr);
+        for (int m = 0; m < M; ++m) NEED4("moka_down_bwd", "dA_acc", dA_acc ? dA_acc[g * M + m] : nullptr);
+    }
     if (dropout_p != 0.f && !seeds) return fail(MOKA_EINVAL, "moka_down_bwd: dropout without seeds");
     DropArgs drop[MOKA_MAX_GROUP];
     for (int g = 0; g < G; ++g) {
@@ -700,6 +769,13 @@ int moka_down_bwd_da_batch(const void* const* dh_kmj, const void* const* x, cons
     if (!dh_kmj || !x || !d_in || !tok_mod || !dA_acc) return fail(MOKA_EINVAL, "moka_down_bwd_da_batch: null pointer");
     if (dropout_p != 0.f && !seeds) return fail(MOKA_EINVAL, "moka_down_bwd_da_batch: dropout without seeds");
     if (dtype != MOKA_BF16) return fail(MOKA_EINVAL, "moka_down_bwd_da_batch: bf16 storage only (fp32 storage: one moka_down_bwd call per projection)");
+    if (M < 1 || M > MOKA_MAX_MOD) return fail(MOKA_EINVAL, "moka_down_bwd_da_batch: M=%d not in 1..%d", M, MOKA_MAX_MOD);
+    NEED16("moka_down_bwd_da_batch", "tok_mod", tok_mod);
+    for (int i = 0; i < n; ++i) {                        // (every problem before the first launch: the deterministic mode launches one at a time)
+        NEED16("moka_down_bwd_da_batch", "dh_kmj", dh_kmj[i]);
+        NEED16("moka_down_bwd_da_batch", "x", x[i]);
+        for (int m = 0; m < M; ++m) NEED4("moka_down_bwd_da_batch", "dA_acc", dA_acc[i * M + m]);
+    }
     if (int drc = check_det_opts("moka_down_bwd_da_batch", opts, false, T, 32, r, 1, M)) return drc;
     if (opts_view(opts).det_ws) {                        // deterministic mode: the per-run partial tiles are sized per call
         for (int i = 0; i < n; ++i) {

@@ -49,6 +49,14 @@ def _storage(tensors, names) -> int:
     raise _lib.MokaError(f"moka_amd: operands must be all bf16 or all fp32 on the HIP path ({desc})")
 
 
+def _dense(t: torch.Tensor) -> torch.Tensor:
+    """`t` as the kernels take an operand: contiguous AND on a 16-byte boundary (include/moka_hip.h, pointer alignment) -- a copy where it
+    is not.  A contiguous view at an odd element offset of a packed buffer is as unusable as a strided one: the library refuses it."""
+    if t.is_contiguous():
+        return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+    return t.contiguous()
+
+
 def _ptrs(tensors: Sequence[torch.Tensor]):
     arr = (c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
     return arr
@@ -564,13 +572,11 @@ class MokaLinearFn(torch.autograd.Function):
         if len(spec.s_out) != rt.M or len(A) != rt.M:
             raise ValueError(f"routing describes {rt.M} modalities but {len(A)} adapters / {len(spec.s_out)} scales were given")
         d_in = x.shape[-1]
-        x2 = x.reshape(-1, d_in)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
+        x2 = _dense(x.reshape(-1, d_in))
         if x2.shape[0] != rt.T:
             raise ValueError(f"x has {x2.shape[0]} tokens but the masks describe {rt.T}")
-        A = [a if a.is_contiguous() else a.contiguous() for a in A]
-        Bw_c = Bw if Bw.is_contiguous() else Bw.contiguous()
+        A = [_dense(a) for a in A]
+        Bw_c = _dense(Bw)
         fused = (dt == _lib.MOKA_BF16 and FUSE_FORWARD and
                  _lib.up_fwd_fused_pays(x2.shape[0], _lib.ksplit(x2.shape[0], d_in, spec.r), [Bw.shape[0]], spec.r, dt))
         kept = spec.shadows if dt == _lib.MOKA_BF16 else None          # persistent (BwT, AT) of the weights' owner
@@ -607,9 +613,7 @@ class MokaLinearFn(torch.autograd.Function):
         x2, W, Bw, h, hp_kmj, BwT, AT, *A = ctx.saved_tensors
         rt, spec = ctx.rt, ctx.spec
         r = spec.r
-        gy2 = gy.reshape(-1, gy.shape[-1])
-        if not gy2.is_contiguous():
-            gy2 = gy2.contiguous()
+        gy2 = _dense(gy.reshape(-1, gy.shape[-1]))
         need_x = ctx.needs_input_grad[0]
         need_B = ctx.needs_input_grad[3]
         need_A = any(ctx.needs_input_grad[6:])
@@ -620,6 +624,10 @@ class MokaLinearFn(torch.autograd.Function):
             dB_acc = spec.sinks[0] if need_B else None
             dA_acc = list(spec.sinks[1]) if need_A else None
             _check_sinks(dB_acc, dA_acc, Bw.shape[0], r, x2.shape[1], len(A), gy2.device)
+            if need_A:
+                # one launch fills the accumulators of ALL modalities: an A_m that asked for no gradient gets a scratch one, so that its
+                # sink (somebody else's slice of a flat buffer) keeps its bits
+                dA_acc = [t if ctx.needs_input_grad[6 + m] else torch.zeros_like(t) for m, t in enumerate(dA_acc)]
             flat, shapes = None, []
         else:
             shapes = ([(Bw.shape[0], r)] if need_B else []) + ([(r, x2.shape[1])] * len(A) if need_A else [])
@@ -713,13 +721,11 @@ class MokaLinearGroupFn(torch.autograd.Function):
         if len(sp.s_out) != rt.M or M != rt.M:
             raise ValueError(f"routing describes {rt.M} modalities but {M} adapters / {len(sp.s_out)} scales were given")
         d_in = x.shape[-1]
-        x2 = x.reshape(-1, d_in)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
+        x2 = _dense(x.reshape(-1, d_in))
         if x2.shape[0] != rt.T:
             raise ValueError(f"x has {x2.shape[0]} tokens but the masks describe {rt.T}")
-        As = [[a if a.is_contiguous() else a.contiguous() for a in Ag] for Ag in As]
-        Bws = [b if b.is_contiguous() else b.contiguous() for b in Bws]
+        As = [[_dense(a) for a in Ag] for Ag in As]
+        Bws = [_dense(b) for b in Bws]
         seeds = [s_.seed for s_ in specs]
         need_x = ctx.needs_input_grad[0]
         fused = FUSE_FORWARD and _lib.up_fwd_fused_pays(x2.shape[0], _lib.ksplit(x2.shape[0], d_in, sp.r, len(Bws)), [b.shape[0] for b in Bws], sp.r)
@@ -775,7 +781,7 @@ class MokaLinearGroupFn(torch.autograd.Function):
             if t_ is None:                                           # an output that did not reach the loss
                 t_ = torch.zeros((x2.shape[0], Ws[g].shape[0]), dtype=x2.dtype, device=dev)
             t_ = t_.reshape(-1, t_.shape[-1])
-            gy2.append(t_ if t_.is_contiguous() else t_.contiguous())
+            gy2.append(_dense(t_))
         need_x = nig[0]
         need_B = any(nig[base + g * per + 2] for g in range(G))
         need_A = any(nig[base + g * per + 3 + m] for g in range(G) for m in range(M))
@@ -785,8 +791,10 @@ class MokaLinearGroupFn(torch.autograd.Function):
                 _check_sinks(specs[g].sinks[0] if need_B else None, list(specs[g].sinks[1]) if need_A else None,
                              Bws[g].shape[0], r, x2.shape[1], M, dev)
             shapes, flat = [], None
-            acc = ([specs[g].sinks[0] for g in range(G)] if need_B else []) + \
-                  ([a_ for g in range(G) for a_ in specs[g].sinks[1]] if need_A else [])
+            # (one launch fills the accumulators of the whole group: a parameter that asked for no gradient gets a scratch one and its sink
+            #  keeps its bits -- see MokaLinearFn.backward)
+            acc = ([specs[g].sinks[0] if nig[base + g * per + 2] else torch.zeros_like(specs[g].sinks[0]) for g in range(G)] if need_B else []) + \
+                  ([a_ if nig[base + g * per + 3 + m] else torch.zeros_like(a_) for g in range(G) for m, a_ in enumerate(specs[g].sinks[1])] if need_A else [])
         else:
             shapes = ([(Bws[g].shape[0], r) for g in range(G)] if need_B else []) + ([(r, x2.shape[1])] * (G * M) if need_A else [])
             flat, acc = _grad_accumulators(shapes, dev) if shapes else (None, [])

@@ -272,25 +272,46 @@ def routing_for_samples(B: int, S: int, samples: Sequence[int], device) -> MokaR
     return MokaRouting(MokaRouting._pad_tok_mod(tok), kpos, klen, B, S, 0, 1)
 
 
-_OVERRIDE = threading.local()
+class _Override:
+    """The routing override of the PROCESS (one slot, guarded by a lock), not of a thread: autograd runs the backward nodes of a device --
+    and with them the re-forward of every checkpointed layer -- on its own device thread, which a ``threading.local`` set by the thread that
+    called ``.backward()`` never reaches."""
+
+    def __init__(self):
+        self.lock = threading.Lock()
+        self.rt: Optional["MokaRouting"] = None
+
+    def swap(self, rt: Optional["MokaRouting"]) -> Optional["MokaRouting"]:
+        with self.lock:
+            prev, self.rt = self.rt, rt
+        return prev
+
+    def get(self) -> Optional["MokaRouting"]:
+        with self.lock:
+            return self.rt
+
+
+_OVERRIDE = _Override()
 
 
 class use_routing:
-    """``with use_routing(rt): model(...)``: every masked adapter call of this thread takes ``rt`` instead of compiling the masks it is
-    handed (``RoutingCache.get``).  What a captured training step needs (``schedule.GraphedTrainStep``): compiling masks reads the device
-    back once per batch, which a stream capture forbids -- the step's routing lives in ``StaticRouting`` buffers the graph's launches point
-    at, refreshed from the batch's masks before every replay."""
+    """``with use_routing(rt): model(...)``: every masked adapter call of the process takes ``rt`` instead of compiling the masks it is
+    handed (``RoutingCache.get``) -- on whichever thread it runs: the calling thread's forward, and the re-forward of a checkpointed layer
+    that autograd runs on its device thread while the block is held open across ``.backward()``.  What a captured training step needs
+    (``schedule.GraphedTrainStep``): compiling masks reads the device back once per batch, which a stream capture forbids -- the step's
+    routing lives in ``StaticRouting`` buffers the graph's launches point at, refreshed from the batch's masks before every replay.
+    Blocks nest (the outer value comes back on exit); two threads that open blocks of their own at the same time share the one slot, so
+    a process runs one overridden step at a time."""
 
     def __init__(self, rt: Optional["MokaRouting"]):
         self.rt = rt
 
     def __enter__(self):
-        self.prev = getattr(_OVERRIDE, "rt", None)
-        _OVERRIDE.rt = self.rt
+        self.prev = _OVERRIDE.swap(self.rt)
         return self.rt
 
     def __exit__(self, *exc):
-        _OVERRIDE.rt = self.prev
+        _OVERRIDE.swap(self.prev)
         return False
 
 
@@ -384,7 +405,7 @@ class RoutingCache:
         self._items.clear()
 
     def get(self, kind: str, masks: Sequence[torch.Tensor]) -> MokaRouting:
-        ov = getattr(_OVERRIDE, "rt", None)
+        ov = _OVERRIDE.get()
         if ov is not None:                       # (use_routing: a captured step's static routing)
             return ov
         key = self._key(kind, masks)

@@ -845,11 +845,17 @@ class GraphedTrainStep:
 
     # ---- what AdapterDataParallel calls while this step is being captured
     def layer_done(self, dp, l: int) -> None:
+        cur = torch.cuda.current_stream(self.dev)
         ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.dev))                 # (the chain's stream: its in-chain gradients of the layer are in front of it)
-        evs = self._reports.setdefault(l, [])
-        evs.append(ev)
-        if self.opt_in_graph and len(evs) == self.n and dp.bucket.is_bucket_first(l):
+        ev.record(cur)                                                 # (the chain's stream: its in-chain gradients of the layer are in front of it)
+        # one report per CHAIN counts: a non-reentrant activation checkpoint runs the layer's forward pre-hook twice (the recording forward and
+        # the re-forward inside the backward), so the layer's input carries two gradient hooks and a chain reports the layer twice -- counted
+        # as two chains, the bucket's AdamW slice ran before the other chain's gradients had been added
+        by_chain = self._reports.setdefault(l, {})
+        first = cur.cuda_stream not in by_chain
+        by_chain[cur.cuda_stream] = ev
+        evs = list(by_chain.values())
+        if self.opt_in_graph and first and len(evs) == self.n and dp.bucket.is_bucket_first(l):
             if self.hub != torch.cuda.current_stream(self.dev):      # (a one-chain capture is a single list: the reports are in stream order already)
                 for e_ in evs:
                     self.hub.wait_event(e_)

@@ -12,24 +12,60 @@ sys.path.insert(0, ROOT)
 pytestmark = pytest.mark.gpu
 
 
-class TinyLM(torch.nn.Module):
-    """projector -> 2 adapted decoder layers -> frozen head, MSE loss; takes the AVT mask list as batch columns."""
+def _checkpointed_stack_cls(use_reentrant):
+    """MokaLlamaStack with every decoder layer's __call__ under torch.utils.checkpoint, the way HF's
+    ``self._gradient_checkpointing_func(decoder_layer.__call__, hidden_states, ...)`` runs it (the reference trains with
+    ``--gradient_checkpointing True``): positional arguments, default RNG-state preservation, the layer's hidden states as the output."""
+    from torch.utils.checkpoint import checkpoint
+    from moka_amd.decoder import MokaLlamaStack, rotary_tables
 
-    def __init__(self, dev, dtype=torch.bfloat16, seed=13):
+    class CheckpointedStack(MokaLlamaStack):
+        def forward(self, h, *mask_args, kv_caches=None, grouped=True, on_layer=None):
+            assert kv_caches is None
+            cos, sin = rotary_tables(h.shape[1], self.dims.head_dim, self.dims.rope_theta, h.device, h.dtype)
+            for i, layer in enumerate(self.layers):
+                h = checkpoint(lambda *a, layer=layer: layer.__call__(*a, grouped=grouped)[0], h, cos, sin, *mask_args, use_reentrant=use_reentrant)
+                if on_layer is not None:
+                    on_layer(i)
+            return h, None
+    return CheckpointedStack
+
+
+class TinyLM(torch.nn.Module):
+    """projector -> 2 adapted decoder layers -> frozen head, MSE loss; takes the AVT mask list as batch columns.
+    variant "vt": the modified_peft mirror (text / image adapters; the audio tokens of the batch belong to no modality).
+    checkpoint: None, or the ``use_reentrant`` of an activation checkpoint around every decoder layer."""
+
+    def __init__(self, dev, dtype=torch.bfloat16, seed=13, variant="avt", lora_dropout=0.0, checkpoint=None):
         super().__init__()
         from moka_amd.decoder import LlamaDims, MokaLlamaStack
-        from moka_amd.peft_hyper import Linear
         self.dims = LlamaDims(hidden=128, ff=256, n_heads=4, n_kv_heads=4)
+        self.variant = variant
         torch.manual_seed(seed)
 
-        def make(d_in, d_out):
-            m = Linear(d_in, d_out, r=(8, 8, 8), lora_alpha=16, lora_nums=3, blc_weight=1.0, blc_alpha=1, lora_dropout=0.0,
-                       loramethod="train", bias=False)
-            torch.nn.init.normal_(m.weight, std=0.05)
-            torch.nn.init.normal_(m.lora_B0.weight, std=0.05)
-            return m
+        if variant == "avt":
+            from moka_amd.peft_hyper import Linear
+
+            def make(d_in, d_out):
+                m = Linear(d_in, d_out, r=(8, 8, 8), lora_alpha=16, lora_nums=3, blc_weight=1.0, blc_alpha=1, lora_dropout=lora_dropout,
+                           loramethod="train", bias=False)
+                torch.nn.init.normal_(m.weight, std=0.05)
+                torch.nn.init.normal_(m.lora_B0.weight, std=0.05)
+                return m
+        else:
+            from moka_amd.modified_peft import Linear as VTLinear
+
+            def make(d_in, d_out):                                   # (tests/test_gpu_dp.py:_build)
+                base = torch.nn.Linear(d_in, d_out, bias=False)
+                torch.nn.init.normal_(base.weight, std=0.05)
+                m = VTLinear(base, "image", r=8, lora_alpha=16, lora_dropout=lora_dropout, attn_weight=0.05)
+                m.update_layer("text", 8, lora_alpha=16, lora_dropout=lora_dropout, init_lora_weights=True, use_rslora=False)
+                m.set_adapter(["image", "text"])
+                for n in ("image", "text"):
+                    torch.nn.init.normal_(m.lora_B[n].weight, std=0.05)
+                return m
         self.vl_projector = torch.nn.Linear(40, self.dims.hidden)
-        self.model = MokaLlamaStack(self.dims, 2, make)
+        self.model = (MokaLlamaStack if checkpoint is None else _checkpointed_stack_cls(bool(checkpoint)))(self.dims, 2, make)
         self.head = torch.nn.Linear(self.dims.hidden, 8)
         self.to(dev, dtype).train()
         for n, p in self.named_parameters():
@@ -37,6 +73,10 @@ class TinyLM(torch.nn.Module):
 
     def forward(self, feats, target, m_t, m_v, m_a, m_q):
         h = self.vl_projector(feats)
+        if self.variant == "vt":
+            out, _ = self.model(h, m_t.squeeze(-1) == 1, m_v.squeeze(-1) == 1, m_q.squeeze(-1) == 1)
+            loss = (self.head(out).float() - target.float()).square().mean()
+            return {"loss": loss}
         out, _ = self.model(h, [m_t, m_v, m_a, m_q])
         loss = (self.head(out).float() - target.float()).square().mean()
         return {"loss": loss}
@@ -157,13 +197,20 @@ def test_graphed_train_step_equals_the_live_loop(chains):
     """moka_amd.schedule.GraphedTrainStep: the whole step (forward, backward through MokaLinearFn, deferred dA_m, the bucket's AdamW slices
     and weight shadows on the hub, a hooked projector parameter) captured as ONE hub-shaped hipGraph and replayed on changing batches ==
     the live attach() loop on the same batches."""
+    _graphed_equals_live(chains, None)
+
+
+def _graphed_equals_live(chains, checkpoint):
+    """checkpoint: None, or the use_reentrant of an activation checkpoint around every decoder layer of BOTH models."""
+    TinyLM_ = TinyLM if checkpoint is None else (lambda dev: TinyLM(dev, checkpoint=checkpoint))
+    from moka_amd import routing as R
     from moka_amd.parallel import attach
     from moka_amd.routing import MokaRouting
     from moka_amd.schedule import GraphedTrainStep
     dev = torch.device("cuda:0")
     batches = [_batch2(dev, shift=0), _batch2(dev, shift=3)]
     steps, lr = 5, 2e-3
-    ref = TinyLM(dev)
+    ref = TinyLM_(dev)
     dp_r = attach(ref, n_buckets=2, lr=lr, weight_decay=0.01)
     ref_losses = []
     n_rows = batches[0]["feats"].shape[0]
@@ -181,14 +228,32 @@ def test_graphed_train_step_equals_the_live_loop(chains):
             tot += float(loss.detach())
         dp_r.step()
         ref_losses.append(tot)
-    m = TinyLM(dev)
+    m = TinyLM_(dev)
     dp = attach(m, n_buckets=2, lr=lr, weight_decay=0.01)
-    gs = GraphedTrainStep(dp, lambda p: m(**p)["loss"], batches[0], chains=chains,
-                          routing_fn=lambda p: MokaRouting.from_avt_masks([p["m_t"], p["m_v"], p["m_a"], p["m_q"]]))
-    init = attach(TinyLM(dev), n_buckets=2, lr=lr, weight_decay=0.01)
-    assert torch.equal(dp.master, init.master) and dp.optimizer.t == 0 and float(dp.bucket.flat.abs().max()) == 0.0   # the capture's warm-up steps were undone
-    losses = [float(gs(batches[i % 2])) for i in range(steps)]
-    torch.cuda.synchronize()
+    # where the routing of the captured step comes from: StaticRouting.load (the buffers the graph's launches point at) and nothing else --
+    # no mask is compiled by the RoutingCache between the start of the capture and the last replay, on whichever thread a forward runs
+    counts = {"compiled": 0, "loaded": 0}
+    build0, load0 = R.RoutingCache._build, R.StaticRouting.load
+
+    def counting_build(kind, masks):
+        counts["compiled"] += 1
+        return build0(kind, masks)
+
+    def counting_load(self, rt):
+        counts["loaded"] += 1
+        return load0(self, rt)
+    R.RoutingCache._build, R.StaticRouting.load = staticmethod(counting_build), counting_load
+    try:
+        gs = GraphedTrainStep(dp, lambda p: m(**p)["loss"], batches[0], chains=chains,
+                              routing_fn=lambda p: MokaRouting.from_avt_masks([p["m_t"], p["m_v"], p["m_a"], p["m_q"]]))
+        init = attach(TinyLM_(dev), n_buckets=2, lr=lr, weight_decay=0.01)
+        assert torch.equal(dp.master, init.master) and dp.optimizer.t == 0 and float(dp.bucket.flat.abs().max()) == 0.0   # the capture's warm-up steps were undone
+        losses = [float(gs(batches[i % 2])) for i in range(steps)]
+        torch.cuda.synchronize()
+    finally:
+        R.RoutingCache._build, R.StaticRouting.load = staticmethod(build0), load0
+    assert counts["compiled"] == 0, f"{counts['compiled']} mask compilation(s) inside the captured step"
+    assert counts["loaded"] >= chains * (steps + 1)
     assert dp.optimizer.t == steps
     if chains == 1:
         assert losses[0] == ref_losses[0], (losses[0], ref_losses[0])          # same kernels on the same data before any update: the same bits
@@ -198,12 +263,21 @@ def test_graphed_train_step_equals_the_live_loop(chains):
     err = ((dp.master - dp_r.master).norm() / dp_r.master.norm()).item()
     assert err <= 2e-4, err
     o = dp.offsets[dp.names.index("vl_projector.weight")]
-    w0 = TinyLM(dev).vl_projector.weight.float().reshape(-1)
+    w0 = TinyLM_(dev).vl_projector.weight.float().reshape(-1)
     assert (dp.master[o:o + w0.numel()] - w0).abs().max().item() > 1e-4          # the hooked (non-kernel-fed) projector trained inside the graph too
     # the live path still works on the same handle after the capture (the graph state was left clean)
     m(**batches[0])["loss"].backward()
     dp.step()
     torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("use_reentrant", [False, True], ids=["non_reentrant", "reentrant"])
+@pytest.mark.parametrize("chains", [1, 2])
+def test_graphed_train_step_with_checkpointed_layers_equals_the_live_loop(chains, use_reentrant):
+    """The same with every decoder layer under torch.utils.checkpoint in the captured model AND in the live loop: the re-forward of a layer
+    runs on autograd's device thread, inside the captured backward -- it must take the step's StaticRouting there (routing.use_routing is
+    process-wide for the block's duration), not compile masks with a host read-back inside the capture.  Same batches, same bounds."""
+    _graphed_equals_live(chains, use_reentrant)
 
 
 def test_persistent_weight_shadows_equal_per_call_shadows():
@@ -321,3 +395,92 @@ def test_hf_trainer_under_two_ranks_stays_out_of_ddp(tmp_path):
     torch.cuda.synchronize()
     err = ((got[0][0].to(dev) - dp_r.master).norm() / dp_r.master.norm()).item()
     assert err <= 2e-3, err                       # (the hooked bf16 projector gradient is rounded per rank; AdamW at step 1-3 follows its sign)
+
+
+# ------------------------------------------------------------------------------------------
+# activation checkpointing through attach() (the reference trains with --gradient_checkpointing True)
+# ------------------------------------------------------------------------------------------
+def _train_under_attach(variant, p, checkpoint, steps=4, accum=1, opt_in_backward=False):
+    """`steps` optimizer steps of TinyLM under attach() with deterministic weight gradients and one torch seed.  Returns the first loss,
+    the flat gradient after the first step's backward (finish(average=False)), the master after the last step, and -- per step -- the layers
+    bucket.layer_done was called with between the start of the backward(s) and the end of the step's first finish()."""
+    from moka_amd import functional as F
+    from moka_amd.parallel import attach
+    dev = torch.device("cuda:0")
+    rows = _data(n=2 * accum)
+    batches = [{k: v.to(dev) for k, v in _collate(rows[2 * k:2 * k + 2]).items()} for k in range(accum)]
+    m = TinyLM(dev, variant=variant, lora_dropout=p, checkpoint=checkpoint)
+    dp = attach(m, n_buckets=2, lr=2e-3, weight_decay=0.01, optimizer_in_backward=opt_in_backward)
+    shipped, counting = [], [True]
+    inner = dp.bucket.layer_done
+
+    def layer_done(l):
+        if counting[0] and dp.bucket.is_bucket_first(l):
+            shipped.append(l)
+        return inner(l)
+    dp.bucket.layer_done = layer_done
+    first_loss, flat0, per_step = None, None, []
+    torch.manual_seed(1234)
+    F.set_deterministic(True)
+    try:
+        for i in range(steps):
+            shipped.clear()
+            counting[0] = True
+            tot = 0.0
+            for k in range(accum):
+                ctx = dp.no_sync() if k < accum - 1 else torch.enable_grad()
+                with ctx:
+                    loss = m(**batches[k])["loss"] / accum           # (a re-forward inside the backward must not trip _forward_begins)
+                    loss.backward()
+                tot += float(loss.detach())
+            if i == 0 and not opt_in_backward:
+                dp.finish(average=False)
+                torch.cuda.synchronize()
+                first_loss, flat0 = tot, dp.bucket.flat.clone()
+                per_step.append(sorted(shipped))
+                counting[0] = False                                  # (step()'s own finish() goes over the buckets again: nothing is in flight)
+                dp.step()
+            else:
+                dp.step()
+                per_step.append(sorted(shipped))
+                first_loss = tot if i == 0 else first_loss
+            assert not dp._deferred, "deferred weight-gradient launches left behind by step()"
+        torch.cuda.synchronize()
+    finally:
+        F.set_deterministic(False)
+    assert all(s_ == dp.bucket.bucket_firsts() for s_ in per_step), (per_step, dp.bucket.bucket_firsts())   # every bucket exactly once per step
+    assert dp.optimizer.t == steps
+    return first_loss, flat0, dp.master.clone()
+
+
+@pytest.mark.parametrize("variant", ["avt", "vt"])
+@pytest.mark.parametrize("p", [0.0, 0.1], ids=["nodrop", "drop"])
+@pytest.mark.parametrize("use_reentrant", [False, True], ids=["non_reentrant", "reentrant"])
+def test_checkpointed_layers_train_bit_identically_under_attach(use_reentrant, p, variant):
+    """Every decoder layer under torch.utils.checkpoint (the trainable projector in front makes the stack input require grad, which the
+    reentrant form needs -- HF's enable_input_require_grads): the recording forward runs a second time INSIDE the backward, with the sinks,
+    the deferred dA_m, the layer hooks and the per-call dropout seeds all live.  Deterministic weight gradients, one torch seed: first loss,
+    flat gradient after the first backward and master after 4 steps are those of the run without checkpointing, bit for bit; every bucket
+    ships once per backward; nothing deferred is left behind; no 'new forward started' error from the re-forwards."""
+    l0, g0, w0 = _train_under_attach(variant, p, None)
+    l1, g1, w1 = _train_under_attach(variant, p, use_reentrant)
+    assert float(g0.abs().max()) > 0
+    assert l1 == l0, (l1, l0)
+    assert torch.equal(g1, g0), f"flat gradient: {((g1 - g0).norm() / g0.norm()).item():.3e} apart"
+    assert torch.equal(w1, w0), f"master after 4 steps: {((w1 - w0).norm() / w0.norm()).item():.3e} apart"
+
+
+@pytest.mark.parametrize("use_reentrant", [False, True], ids=["non_reentrant", "reentrant"])
+def test_checkpointed_layers_with_the_optimizer_inside_the_backward(use_reentrant):
+    """attach(optimizer_in_backward=True): a finished bucket's AdamW slice (and its weight shadows) is enqueued while the earlier layers'
+    backward -- with checkpointing: their re-forward -- is still to come; the run equals the same run without checkpointing."""
+    l0, _, w0 = _train_under_attach("avt", 0.1, None, opt_in_backward=True)
+    l1, _, w1 = _train_under_attach("avt", 0.1, use_reentrant, opt_in_backward=True)
+    assert l1 == l0 and torch.equal(w1, w0), ((w1 - w0).norm() / w0.norm()).item()
+
+
+@pytest.mark.parametrize("use_reentrant", [False, True], ids=["non_reentrant", "reentrant"])
+def test_checkpointed_layers_accumulate_two_micro_batches_under_no_sync(use_reentrant):
+    l0, g0, w0 = _train_under_attach("avt", 0.1, None, accum=2)
+    l1, g1, w1 = _train_under_attach("avt", 0.1, use_reentrant, accum=2)
+    assert l1 == l0 and torch.equal(g1, g0) and torch.equal(w1, w0), ((w1 - w0).norm() / w0.norm()).item()

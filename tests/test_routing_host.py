@@ -4,7 +4,7 @@ cache and error behaviour of the host side."""
 import pytest
 import torch
 
-from moka_amd.routing import MOD_NONE, MokaRouting, RoutingCache
+from moka_amd.routing import MOD_NONE, MokaRouting, RoutingCache, use_routing
 from oracle import cases as C
 from oracle import moka_oracle as O
 
@@ -103,3 +103,65 @@ def test_routing_cache_with_inference_tensors_views_and_data_rewrites():
     q.data[0, 5] = True
     r2 = vc.get("vt", [t, i, q])
     assert r2 is not r1 and int(r2.klen[0]) == 2
+
+
+def _from_thread(fn):
+    """fn() evaluated on a thread started NOW (as autograd's device thread is: not the thread that opened the block)."""
+    import threading
+    out = {}
+
+    def run():
+        try:
+            out["v"] = fn()
+        except BaseException as e:                                   # noqa: BLE001  (re-raised on the caller's thread)
+            out["e"] = e
+    t = threading.Thread(target=run)
+    t.start()
+    t.join()
+    if "e" in out:
+        raise out["e"]
+    return out["v"]
+
+
+def test_use_routing_is_visible_to_threads_started_inside_the_block():
+    """Autograd runs the backward nodes of a device -- and the re-forward of every checkpointed layer -- on its device thread:
+    the override a captured step holds open across .backward() has to reach RoutingCache.get THERE, for exactly the block's
+    duration, and nested blocks have to give the outer value back."""
+    cache = RoutingCache(capacity=4)
+    t = torch.tensor([[1, 1, 0, 0, 1, 1]], dtype=torch.bool)
+    masks = [t, ~t, torch.tensor([[0, 0, 0, 0, 1, 0]], dtype=torch.bool)]
+    plain = cache.get("vt", masks)
+    n_items = len(cache._items)
+    rt_a = MokaRouting.from_vt_masks(*[m.clone() for m in masks])
+    rt_b = MokaRouting.from_vt_masks(*[m.clone() for m in masks])
+    get = lambda: cache.get("vt", masks)                             # noqa: E731
+    assert _from_thread(get) is plain
+    with use_routing(rt_a):
+        assert get() is rt_a and _from_thread(get) is rt_a
+        with use_routing(rt_b):
+            assert get() is rt_b and _from_thread(get) is rt_b
+            with use_routing(None):                                  # None switches the override off for the inner block
+                assert get() is plain and _from_thread(get) is plain
+            assert get() is rt_b and _from_thread(get) is rt_b
+        assert get() is rt_a and _from_thread(get) is rt_a           # the outer value is back
+    assert get() is plain and _from_thread(get) is plain             # and none after the block
+    assert len(cache._items) == n_items                              # nothing was compiled while an override was in force
+
+
+def test_use_routing_of_one_part_is_gone_when_the_next_part_runs():
+    """schedule.GraphedTrainStep runs its parts one after the other, each inside its own block (forward AND backward): what part 0's
+    block set must not be what a thread of part 1 -- or of no part -- reads; an exception inside the block restores as well."""
+    cache = RoutingCache(capacity=4)
+    t = torch.tensor([[1, 1, 0, 0, 1, 1]], dtype=torch.bool)
+    masks = [t, ~t, torch.tensor([[0, 0, 0, 0, 1, 0]], dtype=torch.bool)]
+    plain = cache.get("vt", masks)
+    rts = [MokaRouting.from_vt_masks(*[m.clone() for m in masks]) for _ in range(2)]
+    get = lambda: cache.get("vt", masks)                             # noqa: E731
+    for c in range(2):
+        with use_routing(rts[c]):
+            assert _from_thread(get) is rts[c] and get() is rts[c]
+        assert _from_thread(get) is plain and get() is plain
+    with pytest.raises(RuntimeError, match="inside"):
+        with use_routing(rts[0]):
+            raise RuntimeError("inside")
+    assert _from_thread(get) is plain and get() is plain

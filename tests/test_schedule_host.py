@@ -70,6 +70,8 @@ def test_static_routing_holds_a_batch_routing_at_fixed_addresses():
 
 
 def test_use_routing_overrides_the_mask_compilation_of_this_thread_only():
+    """(The name is history: the override is process-wide since autograd's device thread has to see it -- a thread started inside the
+    block takes the static routing as well; tests/test_routing_host.py pins the thread visibility in detail.)"""
     import threading
     from moka_amd.routing import GLOBAL_ROUTING_CACHE, MokaRouting, StaticRouting, use_routing
     m1, m2 = _masks(1, 64, 40, 50), _masks(1, 64, 30, 34)
@@ -84,7 +86,7 @@ def test_use_routing_overrides_the_mask_compilation_of_this_thread_only():
         with use_routing(None):
             assert GLOBAL_ROUTING_CACHE.get("avt", m2) is plain
         assert GLOBAL_ROUTING_CACHE.get("avt", m2) is st
-    assert GLOBAL_ROUTING_CACHE.get("avt", m2) is plain and seen["other"] is plain
+    assert GLOBAL_ROUTING_CACHE.get("avt", m2) is plain and seen["other"] is st
 
 
 def test_effective_seed_is_the_documented_combination():
