@@ -111,6 +111,8 @@ class AdapterUnit:
         do = I(self.d_outs)
         tm = rt.tok_mod.data_ptr()
         self.keep = (members, A, dA, Bw, dB, y, h, hp_kmj, BwT, AT, part, hp_tok, dh_tok, dh_kmj, ws, so, sds, do, x, dx, seed_dev)
+        # (read-only, for checkers: what the argument lists below were built from -- tests/schedule_oracle.py)
+        self.members, self.x, self.dx, self.seeds = members, x, dx, [int(v) for v in seeds]
         # (defer_da layer: the dA_m halves of a whole decoder layer as one moka_down_bwd_da_batch launch)
         self.da_items = [((own_dh_kmj[g] if own_dh_kmj is not None else scratch[g]["dh_kmj"]), x, self.d_in, members[g]["dA"], seeds[g]) for g in range(G)]
         self.sh_items = [(m["Bw"], m["d_out"], m["A"], self.d_in, m["BwT"], m["AT"]) for m in members]
@@ -583,9 +585,14 @@ class GraphedAdapterStep:
                         hub_opt(l, evs)
         self._keep.append(hc)                            # (streams kept alive with the graph)
 
-    def capture(self) -> bool:
+    def capture(self, restore_grad: bool = False) -> bool:
         """Warm-up launches on a side stream (LDS attributes, lazy module load), then the capture.  Returns True when the step will be
-        replayed from hipGraph(s); on a capture failure the step is launched live (every launch of every chain still happens)."""
+        replayed from hipGraph(s); on a capture failure the step is launched live (every launch of every chain still happens).
+        The warm-up is one live forward + backward of every chain, not a step.  restore_grad=True: the flat gradient is saved in front of it
+        and put back behind it, so the first step's AdamW slices (which, inside the backward, nothing zeroes the buffer for) see that step's
+        gradient alone: what a caller that trains from step 1 passes.  The default leaves the warm-up's dA_m / dB in the buffer, as
+        bench.py has always run it (its first warm-up step consumes them; the parameters it dumps depend on that).  Either way the
+        warm-up adds its adapter terms to the caller's y / dx, which the frozen base rewrites in a real step."""
         cfg, lib, wl, opt, bucket, L, dev = self.cfg, self.lib, self.wl, self.opt, self.bucket, self.L, self.dev
         if cfg.graph == "off":
             return False
@@ -594,12 +601,20 @@ class GraphedAdapterStep:
             # dependency chain goes first (7B r = 16, same box twice: 33.43-33.48 -> 33.16-33.18 ms; r = 64: no difference)
             pri = -1 if cfg.chain_priority == "high" else 0
             side = torch.cuda.Stream(device=dev, priority=pri)
+            grad0 = None
+            if restore_grad:
+                torch.cuda.synchronize()
+                grad0 = bucket.flat.clone()
             with torch.cuda.stream(side):
                 spw = c_void_p(side.cuda_stream)
                 for ch in self.chains:
                     run_forward(lib, ch, spw)
                     run_backward(lib, ch, spw, L)        # warm-up on the capture stream
             torch.cuda.synchronize()
+            if grad0 is not None:
+                bucket.flat.copy_(grad0)                 # (the warm-up is not a step: no gradient of it in the accumulators)
+                del grad0
+                torch.cuda.synchronize()
             self._stagger_buf = torch.empty(max(1, cfg.chain_stagger * (1 << 20) * max(1, cfg.chains - 1)), dtype=torch.uint8, device=dev)
             if os.environ.get("MOKA_BENCH_FAIL_CAPTURE") == "1":
                 raise RuntimeError("MOKA_BENCH_FAIL_CAPTURE=1 (test hook: exercise the live fallback)")

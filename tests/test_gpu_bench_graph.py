@@ -1,5 +1,6 @@
 """The schedules bench.py captures (part-batch chains on forked streams, deferred dA_m on the hub, per-bucket graphs) compute what
-the same launches compute live on one stream: `bench.py --verify-graph` (graph replay vs live, from the same activation state)."""
+the same launches compute live on one stream: `bench.py --verify-graph` (graph replay vs live, from the same activation state).
+Correctness of that step against the fp64 oracle: tests/test_gpu_schedule_oracle.py."""
 import json
 import os
 import subprocess
