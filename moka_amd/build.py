@@ -2,6 +2,8 @@
 
     python -m moka_amd.build [--force] [--diag] [--unity]
 
+and of libmoka_decode.so, the decode-step kernel (csrc/moka_decode.hip, one translation unit), beside it.
+
 The library is six translation units (moka_amd/csrc/k_*.hip: one per kernel family, moka_api.hip: the entry points and launch rules)
 compiled in parallel and linked; a change to the launch rules rebuilds in seconds, a change to one kernel family rebuilds that family.
 ``--unity`` compiles csrc/moka_kernels.hip (all of them in one) instead.  The .so is git-ignored but travels to the GPU box with the
@@ -23,6 +25,8 @@ HEADERS = [os.path.join(CSRC, "moka_device.h"), os.path.join(CSRC, "moka_host.h"
 SRC = os.path.join(CSRC, "moka_kernels.hip")               # the unity form (tools/microbench/passlab.hip, tools/kernel_resources.sh)
 OUT = os.path.join(HERE, "libmoka_hip.so")
 OUT_DIAG = os.path.join(HERE, "libmoka_hip_diag.so")       # -DMOKA_DIAGNOSTICS: moka_tune() launch-heuristic overrides (tools/ only)
+DECODE_SRC = os.path.join(CSRC, "moka_decode.hip")         # the decode-step kernel: a library of its own (include/moka_decode.h)
+OUT_DECODE = os.path.join(HERE, "libmoka_decode.so")
 INC = os.path.join(ROOT, "include")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-function", "-munsafe-fp-atomics", "-I", INC, "-I", CSRC]
 
@@ -45,18 +49,37 @@ def needs_build(out: str = OUT) -> bool:
     return os.path.getmtime(out) < max(os.path.getmtime(p) for p in sources())
 
 
-def _run(cmd, verbose):
+def _run(cmd, verbose, what="libmoka_hip.so"):
     if verbose:
         print(" ".join(cmd), flush=True)
     res = subprocess.run(cmd, capture_output=True, text=True)
     if res.returncode != 0:
         sys.stderr.write(res.stdout + res.stderr)
-        raise RuntimeError("hipcc failed building libmoka_hip.so")
+        raise RuntimeError("hipcc failed building " + what)
+
+
+def decode_sources():
+    """Every file libmoka_decode.so is built from.  Kept apart from ``sources()``: that list is what the traffic summaries of
+    libmoka_hip.so are stamped with, and the decode kernel is no part of that library."""
+    return [DECODE_SRC, os.path.join(ROOT, "include", "moka_decode.h")] + HEADERS
+
+
+def build_decode(force: bool = False, verbose: bool = True) -> str:
+    """libmoka_decode.so (include/moka_decode.h): the decode-step adapter kernel, one translation unit compiled and linked in one go."""
+    srcs = decode_sources()
+    if not force and os.path.exists(OUT_DECODE) and os.path.getmtime(OUT_DECODE) >= max(os.path.getmtime(p) for p in srcs):
+        return OUT_DECODE
+    _run([_hipcc()] + FLAGS + ["-shared", DECODE_SRC, "-o", OUT_DECODE + ".tmp"], verbose, "libmoka_decode.so")
+    os.replace(OUT_DECODE + ".tmp", OUT_DECODE)
+    return OUT_DECODE
 
 
 def build(force: bool = False, verbose: bool = True, diag: bool = False, unity: bool = False) -> str:
-    """diag: the diagnostics variant (same ABI + working moka_tune), loaded by the tools through MOKA_HIP_LIB."""
+    """diag: the diagnostics variant (same ABI + working moka_tune), loaded by the tools through MOKA_HIP_LIB.  The product variant
+    also brings libmoka_decode.so up to date (``build_decode``); the path returned is libmoka_hip.so's."""
     out = OUT_DIAG if diag else OUT
+    if not diag:
+        build_decode(force=force, verbose=verbose)
     if not force and not needs_build(out):
         return out
     cc, defs = _hipcc(), (["-DMOKA_DIAGNOSTICS"] if diag else [])

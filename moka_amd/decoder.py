@@ -236,8 +236,15 @@ class MokaLlamaStack(nn.Module):
 
     def merge_for_decode(self) -> None:
         """Pre-compute ``decode_weight`` of all 7 x L projections (inference only; call again after the adapter changed).
-        Decode steps (``kv_caches`` given, past > 0) then run one GEMM per projection instead of base GEMM + three adapter
-        launches; prefill and training are unaffected."""
+        Decode steps (``kv_caches`` given, past > 0) then run one GEMM per projection instead of base GEMM + adapter launches;
+        prefill and training are unaffected.
+
+        When to merge: with ``functional.DECODE_FORWARD`` on, an un-merged decode step costs one extra launch per projection group
+        (``moka_decode_fwd``, include/moka_decode.h: four per layer; twelve on the general path, the default), needs no second copy of the weights and follows the adapter as it changes.  Merging
+        removes that launch too, at the price of a dense copy of every projection weight (about 13 GB at the 7B widths, 130 GB at 70B)
+        that has to be rebuilt whenever the adapter changes -- worth it for long generations with a frozen adapter where the memory
+        is free, for more than ``moka_decode_max_tokens()`` tokens per step, and for fp32 storage, which the decode kernel does not
+        serve.  The merged weight rounds ``W + s B A`` to bf16 once, so its outputs differ from the adapter path's in the last bits."""
         self._merged = {}
         for layer in self.layers:
             a, m = layer.self_attn, layer.mlp

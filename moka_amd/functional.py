@@ -13,7 +13,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-from . import _lib
+from . import _decode_lib, _lib
 from .routing import MokaRouting
 
 
@@ -524,6 +524,62 @@ def _split_like(flat: torch.Tensor, shapes: Sequence[Tuple[int, int]]) -> List[t
 # (tests/test_gpu_fused.py); a module-level switch for A/B runs, not a tuning knob.
 FUSE_FORWARD = True
 
+# Cached decode steps (masks None, no autograd, a handful of tokens): True = the base GEMMs + ONE moka_decode_fwd launch per
+# projection group (include/moka_decode.h: no split-K slices, no backward state, no weight shadows); False (default) = the autograd nodes
+# below, as for training.  A module-level switch for A/B runs (tools/decode_step.py), not a tuning knob.  It ships OFF: the kernel is
+# tested for correctness, but no timing of it against the general path is recorded yet ("Cached decode steps"); the
+# default turns on with that record.
+DECODE_FORWARD = False
+decode_launches = 0      # moka_decode_fwd calls made by moka_linear / moka_linear_group so far (tests and tools/decode_step.py read it)
+
+
+def decode_serves(switch_on: bool, is_plain: bool, dtype: int, dropout_ps: Sequence[float], grad_recorded: bool,
+                  T: int, d_in: int, d_outs: Sequence[int], r: int) -> bool:
+    """Does the decode-step kernel take this call?  Plain values in, so the rule can be checked without a device: the switch is on, the
+    routing is ``MokaRouting.plain``, bf16 storage, no dropout, autograd records nothing, and the library accepts the shape
+    (moka_decode_ok: at most moka_decode_max_tokens tokens, at most three projections)."""
+    if not (switch_on and is_plain) or dtype != _lib.MOKA_BF16 or grad_recorded or any(p > 0.0 for p in dropout_ps):
+        return False
+    return _decode_lib.decode_ok(T, d_in, d_outs, r, dtype)
+
+
+def _decode_forward(x, projections, rt: MokaRouting, specs):
+    """The outputs of a plain-routing call on the decode-step kernel, or None when the call belongs to the autograd nodes (which also
+    raise the errors of a malformed call).  Gathers the plain values of the call and asks ``decode_serves`` once.
+
+    "Autograd records nothing" is judged per call, so a no-grad pass over TRAINABLE adapters is a decode call as well: under reentrant
+    activation checkpointing the first forward of a masks-None call of at most moka_decode_max_tokens tokens takes this kernel and the
+    recompute takes the autograd node.  The two outputs agree to the last bits of bf16 (tests/test_gpu_decode.py: both are within one ulp
+    of the oracle), the gradients are those of the node; set DECODE_FORWARD = False where bit-equal recomputation matters."""
+    sp = specs[0]
+    tensors = []
+    for (W, b, Bw, A), o in zip(projections, specs):
+        if W is None or len(A) != rt.M or len(o.s_out) != rt.M:          # adapter term alone / a malformed call: not one fused call
+            return None
+        if (o.r, o.s_in, o.s_out) != (sp.r, sp.s_in, sp.s_out):          # one rank and one scale per launch
+            return None
+        tensors += [W, Bw, *A] + ([b] if b is not None else [])
+    d_in = x.shape[-1]
+    T = x.numel() // d_in
+    kinds = {t.dtype for t in tensors} | {x.dtype}
+    dtype = {torch.bfloat16: _lib.MOKA_BF16, torch.float32: _lib.MOKA_F32}.get(next(iter(kinds))) if len(kinds) == 1 else None
+    if dtype is None or not x.is_cuda or T != rt.T:
+        return None
+    recorded = torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in tensors))
+    d_outs = [int(Bw.shape[0]) for (_, _, Bw, _) in projections]
+    if not decode_serves(DECODE_FORWARD, rt.is_plain, dtype, [o.dropout_p for o in specs], recorded, T, d_in, d_outs, sp.r):
+        return None
+    global decode_launches
+    x2 = _dense(x.reshape(-1, d_in))
+    ys = [_dense(torch.nn.functional.linear(x2, W, b)) for (W, b, _, _) in projections]      # frozen base, stock PyTorch-ROCm
+    As = [_dense(A[0]) for (_, _, _, A) in projections]                                        # masks None: the text adapter alone
+    Bws = [_dense(Bw) for (_, _, Bw, _) in projections]
+    _decode_lib.check(_decode_lib.load().moka_decode_fwd(x2.data_ptr(), _ptrs(As), _ptrs(Bws), _ptrs(ys), _ints(d_outs), len(ys), T, d_in,
+                                                         sp.r, float(sp.s_in * sp.s_out[0]), _stream_ptr(x2.device)), "moka_decode_fwd")
+    decode_launches += 1
+    return [y.reshape(*x.shape[:-1], y.shape[-1]) for y in ys]
+
+
 # --------------------------------------------------------------------------------------
 # autograd node of one adapted projection
 # --------------------------------------------------------------------------------------
@@ -684,6 +740,10 @@ def moka_linear(x, W, bias, Bw, A: Sequence[torch.Tensor], rt: MokaRouting, spec
         # back onto the tokens they stand for (autograd carries their input gradients the same way); the frozen base sees the real tokens only
         ya = rt.fold(MokaLinearFn.apply(rt.extend(x), None, None, Bw, rt, spec, *A)).reshape(*x.shape[:-1], Bw.shape[0])
         return ya if W is None else torch.nn.functional.linear(x, W, bias) + ya
+    if getattr(rt, "is_plain", False):                   # mask-free call (masked training calls gather nothing for the decode rule): one launch behind the base GEMM where decode_serves says so
+        ys = _decode_forward(x, [(W, bias, Bw, A)], rt, [spec])
+        if ys is not None:
+            return ys[0]
     return MokaLinearFn.apply(x, W, bias, Bw, rt, spec, *A)
 
 
@@ -847,6 +907,10 @@ def moka_linear_group(x, projections, rt: MokaRouting, specs: Sequence[AdapterSp
     """projections: list of (W, bias|None, Bw, [A_0..A_{M-1}]) fed by the same x.  Returns the list of outputs."""
     if x.dtype == torch.float32 or getattr(rt, "dup_src", None) is not None:          # fp32 storage / virtual tokens: correctness paths, one projection at a time
         return [moka_linear(x, W, b, Bw, A, rt, sp) for (W, b, Bw, A), sp in zip(projections, specs)]
+    if getattr(rt, "is_plain", False):                                                   # (see moka_linear)
+        ys = _decode_forward(x, projections, rt, list(specs))
+        if ys is not None:
+            return ys
     G = len(projections)
     M = len(projections[0][3])
     flat = []

@@ -25,6 +25,10 @@ MOD_NONE = _lib.MOKA_MOD_NONE
 class MokaRouting:
     """Device-resident routing of one batch.  ``struct`` is the C view passed to the library."""
 
+    # True only on what ``plain()`` returns: every token through adapter 0, no interaction, nothing skipped -- the one routing the
+    # decode-step kernel serves (functional.decode_serves)
+    is_plain = False
+
     def __init__(self, tok_mod: torch.Tensor, kpos: torch.Tensor, klen: torch.Tensor,
                  B: int, S: int, Lk_max: int, M: int):
         dev = tok_mod.device
@@ -258,7 +262,9 @@ class MokaRouting:
         tok = torch.zeros((B, S), dtype=torch.uint8, device=device)
         kpos = torch.full((B, 1), -1, dtype=torch.int32, device=device)
         klen = torch.zeros((B,), dtype=torch.int32, device=device)
-        return cls(cls._pad_tok_mod(tok), kpos, klen, B, S, 0, M)
+        rt = cls(cls._pad_tok_mod(tok), kpos, klen, B, S, 0, M)
+        rt.is_plain = True
+        return rt
 
 
 def routing_for_samples(B: int, S: int, samples: Sequence[int], device) -> MokaRouting:
