@@ -1,9 +1,11 @@
 """Host glue between torch tensors and the C ABI (include/moka_hip.h).
 
-``ops`` are thin 1:1 wrappers of the exported entry points (pointer extraction, workspace
-allocation, current-stream lookup); ``MokaLinearFn`` is the autograd node of one adapted
-projection: frozen base GEMM on stock PyTorch-ROCm + the MokA adapter on the HIP kernels,
-with the explicit backward the reference leaves to autograd.
+``ops`` are thin 1:1 wrappers of the exported ``moka_X_group`` entry points (pointer extraction,
+workspace allocation, current-stream lookup), each with a one-projection form that calls it with
+lists of one -- as ``moka_X`` does in the library; ``MokaLinearFn`` is the one autograd node of
+1..G adapted projections fed by the same x: frozen base GEMMs on stock PyTorch-ROCm + the MokA
+adapters on the HIP kernels, with the explicit backward the reference leaves to autograd
+(SURVEY.md section 8, rows a11 and f1).
 """
 from __future__ import annotations
 
@@ -32,11 +34,6 @@ def _require_device(t: torch.Tensor, name: str):
             "MI355X (gfx950) -- there is no CPU fallback (use oracle/ for CPU checking).")
 
 
-def _require_bf16(t: torch.Tensor, name: str):
-    if t.dtype != torch.bfloat16:
-        raise _lib.MokaError(f"moka_amd: `{name}` is {t.dtype}; the HIP path stores activations and weights in bf16")
-
-
 def _storage(tensors, names) -> int:
     """Storage dtype code of one adapted projection: all operands bf16 (the tuned path) or all fp32 (MOKA_F32: exact-fp32 FMA
     kernels, the reference's fp32 configuration -- adapters follow the base dtype, layer.py:124-132)."""
@@ -58,8 +55,7 @@ def _dense(t: torch.Tensor) -> torch.Tensor:
 
 
 def _ptrs(tensors: Sequence[torch.Tensor]):
-    arr = (c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-    return arr
+    return (c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
 def _floats(vals: Sequence[float]):
@@ -67,20 +63,21 @@ def _floats(vals: Sequence[float]):
 
 
 # --------------------------------------------------------------------------------------
-# 1:1 wrappers of the C entry points
+# 1:1 wrappers of the C entry points: G projections fed by the same x (q/k/v, gate/up), G >= 1
 # --------------------------------------------------------------------------------------
-def down_fwd(x2: torch.Tensor, A: Sequence[torch.Tensor], rt: MokaRouting, r: int, s_in: float,
-             dropout_p: float = 0.0, seed: int = 0, dtype: int = 0, seed_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """x2 [T,d_in] bf16 -> part [ks,T,RP] fp32 (split-K partials of s_in * drop(x) A_mod^T)."""
-    lib = _lib.load()
-    T, d_in = x2.shape
-    RP = _lib.rank_pad(r)
-    ks = _lib.ksplit(T, d_in, r)
-    part = torch.empty((ks, T, RP), dtype=torch.float32, device=x2.device)
-    _lib.check(lib.moka_down_fwd(x2.data_ptr(), _ptrs(A), rt.tok_mod.data_ptr(), part.data_ptr(),
-                                 T, d_in, r, len(A), float(s_in), float(dropout_p), int(seed), dtype,
-                                 _det_opts(x2.device, T, d_in, r, 1, len(A), seed_dev, want_det=False), _stream_ptr(x2.device)), "moka_down_fwd")
-    return part
+def _ints(vals: Sequence[int]):
+    return (ctypes.c_int * len(vals))(*[int(v) for v in vals])
+
+
+def _u64s(vals: Sequence[int]):
+    return (ctypes.c_ulonglong * len(vals))(*[int(v) for v in vals])
+
+
+def _optptrs(tensors: Optional[Sequence[Optional[torch.Tensor]]]):
+    """A pointer array with NULL for the members that are None; NULL for no array at all."""
+    if tensors is None:
+        return None
+    return (c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
 
 
 class FwdState:
@@ -88,13 +85,9 @@ class FwdState:
     __slots__ = ("h", "hp", "hp_tok", "hp_kmj", "BwT", "AT")
 
 
-def cross_fwd(part: torch.Tensor, rt: MokaRouting, r: int, s_out: Sequence[float], w: float, inv_sqrt_dk: float,
-              Bw: Optional[torch.Tensor] = None, want_hp: bool = False, A: Optional[Sequence[torch.Tensor]] = None,
-              want_tok: bool = True) -> FwdState:
-    """want_tok=False: the token-major pack is not written (the up-projection is `up_fwd_fused_`, which computes it itself)."""
-    lib = _lib.load()
-    ks, T, RP = part.shape
-    dev = part.device
+def _fwd_state(T: int, RP: int, dev, want_hp: bool = False, want_tok: bool = False, Bw: Optional[torch.Tensor] = None,
+               A: Optional[Sequence[torch.Tensor]] = None) -> FwdState:
+    """The buffers one projection's forward writes: h and hp_kmj always; hp / hp_tok on request; the shadows of the weights given."""
     Tp = _lib.tok_pad(T)
     st = FwdState()
     st.h = torch.empty((T, RP), dtype=torch.float32, device=dev)
@@ -103,120 +96,103 @@ def cross_fwd(part: torch.Tensor, rt: MokaRouting, r: int, s_out: Sequence[float
     st.hp_kmj = torch.empty((2, RP, Tp), dtype=torch.bfloat16, device=dev)
     st.BwT = torch.empty((RP, Bw.shape[0]), dtype=torch.bfloat16, device=dev) if Bw is not None else None
     st.AT = torch.empty((len(A), A[0].shape[1], RP), dtype=torch.bfloat16, device=dev) if A is not None else None
-    _lib.check(lib.moka_cross_fwd(part.data_ptr(), ks, byref(rt.struct), _floats(s_out),
-                                  None if Bw is None else Bw.data_ptr(), 0 if Bw is None else Bw.shape[0],
-                                  None if A is None else _ptrs(A), 0 if A is None else A[0].shape[1],
-                                  st.h.data_ptr(), None if st.hp is None else st.hp.data_ptr(),
-                                  None if st.hp_tok is None else st.hp_tok.data_ptr(), st.hp_kmj.data_ptr(),
-                                  None if st.BwT is None else st.BwT.data_ptr(),
-                                  None if st.AT is None else st.AT.data_ptr(),
-                                  r, float(w), float(inv_sqrt_dk), _stream_ptr(dev)), "moka_cross_fwd")
     return st
-
-
-def up_fwd_fused_(y2: torch.Tensor, part: torch.Tensor, Bw: torch.Tensor, rt: MokaRouting, r: int, s_out: Sequence[float],
-                  w: float, inv_sqrt_dk: float, want_state: bool = False) -> Optional[FwdState]:
-    """In place: y2 [T,d_out] bf16 += (s_out[mod] hp) Bw^T with hp computed from the split-K slices `part` inside the kernel
-    (the bits of cross_fwd + up_fwd_; bf16 storage).  want_state: the launch also writes what the backward reads from
-    the rank space (h, hp_kmj); returned as a FwdState whose BwT / AT are filled by `weight_shadows`."""
-    lib = _lib.load()
-    ks, T, RP = part.shape
-    st = None
-    if want_state:
-        st = FwdState()
-        st.h = torch.empty((T, RP), dtype=torch.float32, device=part.device)
-        st.hp_kmj = torch.empty((2, RP, _lib.tok_pad(T)), dtype=torch.bfloat16, device=part.device)
-        st.hp = st.hp_tok = st.BwT = st.AT = None
-    _lib.check(lib.moka_up_fwd_fused(part.data_ptr(), ks, byref(rt.struct), _floats(s_out), Bw.data_ptr(), y2.data_ptr(),
-                                     y2.shape[1], None if st is None else st.h.data_ptr(), None if st is None else st.hp_kmj.data_ptr(),
-                                     r, float(w), float(inv_sqrt_dk), _lib.MOKA_BF16, _stream_ptr(y2.device)),
-               "moka_up_fwd_fused")
-    return st
-
-
-def weight_shadows(Bw: Optional[torch.Tensor], A: Optional[Sequence[torch.Tensor]], r: int) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
-    """(BwT [RP, d_out], AT [M, d_in, RP]) bf16: the transposed, zero-padded weight copies the backward kernels read -- functions of
-    the weights alone (moka_weight_shadows), so they need not sit on the forward's dependency chain."""
-    lib = _lib.load()
-    RP = _lib.rank_pad(r)
-    ref = Bw if Bw is not None else A[0]
-    BwT = torch.empty((RP, Bw.shape[0]), dtype=torch.bfloat16, device=ref.device) if Bw is not None else None
-    AT = torch.empty((len(A), A[0].shape[1], RP), dtype=torch.bfloat16, device=ref.device) if A is not None else None
-    _lib.check(lib.moka_weight_shadows(None if Bw is None else Bw.data_ptr(), 0 if Bw is None else Bw.shape[0],
-                                       None if A is None else _ptrs(A), 0 if A is None else A[0].shape[1],
-                                       None if BwT is None else BwT.data_ptr(), None if AT is None else AT.data_ptr(),
-                                       r, len(A) if A is not None else 1, _stream_ptr(ref.device)), "moka_weight_shadows")
-    return BwT, AT
-
-
-def up_fwd_(y2: torch.Tensor, hp_tok: torch.Tensor, Bw: torch.Tensor, rt: MokaRouting, r: int, dtype: int = 0):
-    """In place: y2 [T,d_out] bf16 += (s_out[mod] hp) Bw^T (the scale is already inside hp_tok)."""
-    lib = _lib.load()
-    T, d_out = y2.shape
-    _lib.check(lib.moka_up_fwd(hp_tok.data_ptr(), Bw.data_ptr(), rt.tok_mod.data_ptr(), y2.data_ptr(),
-                               T, r, d_out, dtype, _stream_ptr(y2.device)), "moka_up_fwd")
-    return y2
-
-
-def up_bwd(gy2: torch.Tensor, hp_kmj: Optional[torch.Tensor], BwT: Optional[torch.Tensor], rt: MokaRouting, r: int,
-           s_out: Sequence[float], dB_acc: Optional[torch.Tensor], dtype: int = 0, want_g: bool = True) -> Optional[torch.Tensor]:
-    """gy2 [T,d_out] bf16 -> g_part [ks,T,RP] (want_g=False: skip); dB_acc [d_out,r] fp32 += (may be None: skip)."""
-    lib = _lib.load()
-    T, d_out = gy2.shape
-    RP = _lib.rank_pad(r)
-    ks = _lib.ksplit_bwd(T, d_out, r)
-    g_part = torch.empty((ks, T, RP), dtype=torch.float32, device=gy2.device) if want_g else None
-    _lib.check(lib.moka_up_bwd(gy2.data_ptr(), None if hp_kmj is None else hp_kmj.data_ptr(), None if BwT is None else BwT.data_ptr(),
-                               rt.tok_mod.data_ptr(), _floats(s_out), None if g_part is None else g_part.data_ptr(),
-                               None if dB_acc is None else dB_acc.data_ptr(),
-                               T, r, d_out, len(s_out), dtype, _det_opts(gy2.device, T, d_out, r, 1, len(s_out)) if dB_acc is not None else None,
-                               _stream_ptr(gy2.device)), "moka_up_bwd")
-    return g_part
 
 
 class BwdState:
     __slots__ = ("dh", "dh_tok", "dh_kmj")
 
 
-def cross_bwd(g_part: torch.Tensor, h: torch.Tensor, rt: MokaRouting, r: int, s_in: float, w: float, inv_sqrt_dk: float,
-              want_dh: bool = False) -> BwdState:
-    lib = _lib.load()
-    ks, T, RP = g_part.shape
-    dev = g_part.device
+def _bwd_state(T: int, RP: int, M: int, dev, want_dh: bool = False) -> BwdState:
     Tp = _lib.tok_pad(T)
     st = BwdState()
     st.dh = torch.empty((T, RP), dtype=torch.float32, device=dev) if want_dh else None
     st.dh_tok = torch.empty((Tp, 2 * RP), dtype=torch.bfloat16, device=dev)
-    st.dh_kmj = torch.empty((rt.M, 2, RP, Tp), dtype=torch.bfloat16, device=dev)
-    _lib.check(lib.moka_cross_bwd(g_part.data_ptr(), ks, h.data_ptr(), byref(rt.struct), float(s_in),
-                                  None if st.dh is None else st.dh.data_ptr(), st.dh_tok.data_ptr(), st.dh_kmj.data_ptr(),
-                                  rt.cross_ws(r).data_ptr(), r, float(w), float(inv_sqrt_dk), _stream_ptr(dev)), "moka_cross_bwd")
+    st.dh_kmj = torch.empty((M, 2, RP, Tp), dtype=torch.bfloat16, device=dev)
     return st
 
 
-def down_bwd_(bst: BwdState, x2: torch.Tensor, AT: Optional[torch.Tensor], rt: MokaRouting, r: int,
-              dA_acc: Optional[Sequence[torch.Tensor]], dx2: Optional[torch.Tensor],
-              dropout_p: float = 0.0, seed: int = 0, dtype: int = 0, seed_dev: Optional[torch.Tensor] = None):
-    """dA_acc[m] [r,d_in] fp32 += ; dx2 [T,d_in] bf16 += (either may be None)."""
+def down_fwd_group(x2: torch.Tensor, A: Sequence[Sequence[torch.Tensor]], rt: MokaRouting, r: int, s_in: float,
+                   dropout_p: float = 0.0, seeds: Optional[Sequence[int]] = None, seed_dev: Optional[torch.Tensor] = None,
+                   dtype: int = _lib.MOKA_BF16) -> List[torch.Tensor]:
+    """One read of x2 [T,d_in] for the G down-projections A[g][m]; returns the G split-K partial buffers
+    part [ks,T,RP] fp32 (the slices of s_in * drop(x) A_mod^T)."""
     lib = _lib.load()
     T, d_in = x2.shape
-    _lib.check(lib.moka_down_bwd(bst.dh_tok.data_ptr(), None if bst.dh_kmj is None else bst.dh_kmj.data_ptr(), x2.data_ptr(),
-                                 None if AT is None else AT.data_ptr(), rt.tok_mod.data_ptr(),
-                                 None if dA_acc is None else _ptrs(dA_acc), None if dx2 is None else dx2.data_ptr(),
-                                 T, d_in, r, rt.M, float(dropout_p), int(seed), dtype,
-                                 _det_opts(x2.device, T, d_in, r, 1, rt.M, seed_dev, want_det=dA_acc is not None),
-                                 _stream_ptr(x2.device)), "moka_down_bwd")
+    G, M = len(A), len(A[0])
+    RP = _lib.rank_pad(r)
+    ks = _lib.ksplit(T, d_in, r, G)
+    parts = [torch.empty((ks, T, RP), dtype=torch.float32, device=x2.device) for _ in range(G)]
+    _lib.check(lib.moka_down_fwd_group(x2.data_ptr(), _ptrs([a for Ag in A for a in Ag]), rt.tok_mod.data_ptr(), _ptrs(parts),
+                                       T, d_in, r, M, G, float(s_in), float(dropout_p),
+                                       _u64s(seeds if seeds is not None else [0] * G), dtype,
+                                       _det_opts(x2.device, T, d_in, r, G, M, seed_dev, want_det=False), _stream_ptr(x2.device)), "moka_down_fwd_group")
+    return parts
 
 
-# --------------------------------------------------------------------------------------
-# grouped entry points: G projections fed by the same x (q/k/v, gate/up)
-# --------------------------------------------------------------------------------------
-def _ints(vals: Sequence[int]):
-    return (ctypes.c_int * len(vals))(*[int(v) for v in vals])
+def cross_fwd_group(parts: Sequence[torch.Tensor], rt: MokaRouting, r: int, s_out: Sequence[float], w: float, inv_sqrt_dk: float,
+                    Bw: Optional[Sequence[torch.Tensor]] = None, A: Optional[Sequence[Sequence[torch.Tensor]]] = None,
+                    want_tok: bool = True, want_hp: bool = False) -> List[FwdState]:
+    """Bw / A: the weights whose shadows (BwT / AT) the launch writes as well; None: neither allocated nor requested.
+    want_tok=False: the token-major pack is not written (the up-projection is `up_fwd_fused_group_`, which computes it itself)."""
+    lib = _lib.load()
+    G = len(parts)
+    ks, T, RP = parts[0].shape
+    dev = parts[0].device
+    sts = [_fwd_state(T, RP, dev, want_hp, want_tok, None if Bw is None else Bw[g], None if A is None else A[g]) for g in range(G)]
+    _lib.check(lib.moka_cross_fwd_group(_ptrs(parts), ks, byref(rt.struct), _floats(s_out),
+                                        _optptrs(Bw), None if Bw is None else _ints([b.shape[0] for b in Bw]),
+                                        None if A is None else _ptrs([a for Ag in A for a in Ag]), 0 if A is None else A[0][0].shape[1],
+                                        _ptrs([st.h for st in sts]), _ptrs([st.hp for st in sts]) if want_hp else None,
+                                        _ptrs([st.hp_tok for st in sts]) if want_tok else None, _ptrs([st.hp_kmj for st in sts]),
+                                        None if Bw is None else _ptrs([st.BwT for st in sts]),
+                                        None if A is None else _ptrs([st.AT for st in sts]),
+                                        G, r, float(w), float(inv_sqrt_dk), _stream_ptr(dev)), "moka_cross_fwd_group")
+    return sts
 
 
-def _u64s(vals: Sequence[int]):
-    return (ctypes.c_ulonglong * len(vals))(*[int(v) for v in vals])
+def up_fwd_group_(ys: Sequence[torch.Tensor], hp_toks: Sequence[torch.Tensor], Bw: Sequence[torch.Tensor], rt: MokaRouting, r: int,
+                  dtype: int = _lib.MOKA_BF16):
+    """In place: ys[g] [T,d_out_g] += (s_out[mod] hp_g) Bw_g^T (the scale is already inside hp_toks[g])."""
+    lib = _lib.load()
+    T = ys[0].shape[0]
+    _lib.check(lib.moka_up_fwd_group(_ptrs(hp_toks), _ptrs(Bw), rt.tok_mod.data_ptr(), _ptrs(ys), T, r,
+                                     _ints([y.shape[1] for y in ys]), len(ys), dtype, _stream_ptr(ys[0].device)),
+               "moka_up_fwd_group")
+
+
+def up_fwd_fused_group_(ys: Sequence[torch.Tensor], parts: Sequence[torch.Tensor], Bw: Sequence[torch.Tensor], rt: MokaRouting, r: int,
+                        s_out: Sequence[float], w: float, inv_sqrt_dk: float, want_state: bool = False) -> Optional[List[FwdState]]:
+    """In place: ys[g] [T,d_out] bf16 += (s_out[mod] hp_g) Bw_g^T with hp_g computed from the split-K slices `parts[g]` inside the kernel
+    (the bits of cross_fwd_group + up_fwd_group_; bf16 storage).  want_state: the launch also writes what the backward reads from
+    the rank space (h, hp_kmj); returned as FwdStates whose BwT / AT are filled by `weight_shadows_group`."""
+    lib = _lib.load()
+    ks, T, RP = parts[0].shape
+    sts = [_fwd_state(T, RP, parts[0].device) for _ in ys] if want_state else None
+    _lib.check(lib.moka_up_fwd_fused_group(_ptrs(parts), ks, byref(rt.struct), _floats(s_out), _ptrs(Bw), _ptrs(ys),
+                                           _ints([y.shape[1] for y in ys]),
+                                           None if sts is None else _ptrs([st.h for st in sts]),
+                                           None if sts is None else _ptrs([st.hp_kmj for st in sts]),
+                                           len(ys), r, float(w), float(inv_sqrt_dk),
+                                           _lib.MOKA_BF16, _stream_ptr(ys[0].device)), "moka_up_fwd_fused_group")
+    return sts
+
+
+def weight_shadows_group(Bws: Optional[Sequence[torch.Tensor]], As: Optional[Sequence[Sequence[torch.Tensor]]], r: int):
+    """Per projection (BwT [RP, d_out], AT [M, d_in, RP]) bf16 in one launch: the transposed, zero-padded weight copies the backward kernels
+    read -- functions of the weights alone (moka_weight_shadows), so they need not sit on the forward's dependency chain.  BwT only when
+    `Bws` is given, AT only when `As` is."""
+    lib = _lib.load()
+    RP = _lib.rank_pad(r)
+    dev = Bws[0].device if Bws is not None else As[0][0].device
+    BwTs = [torch.empty((RP, b.shape[0]), dtype=torch.bfloat16, device=dev) for b in Bws] if Bws is not None else None
+    ATs = [torch.empty((len(Ag), Ag[0].shape[1], RP), dtype=torch.bfloat16, device=dev) for Ag in As] if As is not None else None
+    _lib.check(lib.moka_weight_shadows_group(_optptrs(Bws), None if Bws is None else _ints([b.shape[0] for b in Bws]),
+                                             None if As is None else _ptrs([a for Ag in As for a in Ag]), 0 if As is None else As[0][0].shape[1],
+                                             _optptrs(BwTs), _optptrs(ATs),
+                                             len(Bws if Bws is not None else As), r, len(As[0]) if As is not None else 1, _stream_ptr(dev)),
+               "moka_weight_shadows_group")
+    return BwTs, ATs
 
 
 def weight_shadows_batch_(Bws: Sequence[torch.Tensor], As: Sequence[Sequence[torch.Tensor]], r: int,
@@ -232,102 +208,10 @@ def weight_shadows_batch_(Bws: Sequence[torch.Tensor], As: Sequence[Sequence[tor
                                                  _stream_ptr(Bws[0].device)), "moka_weight_shadows_batch")
 
 
-def _optptrs(tensors: Sequence[Optional[torch.Tensor]]):
-    return (c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
-
-
-def down_fwd_group(x2: torch.Tensor, A: Sequence[Sequence[torch.Tensor]], rt: MokaRouting, r: int, s_in: float,
-                   dropout_p: float = 0.0, seeds: Optional[Sequence[int]] = None, seed_dev: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
-    """One read of x2 [T,d_in] for the G down-projections A[g][m]; returns the G split-K partial buffers."""
-    lib = _lib.load()
-    T, d_in = x2.shape
-    G, M = len(A), len(A[0])
-    RP = _lib.rank_pad(r)
-    ks = _lib.ksplit(T, d_in, r, G)
-    parts = [torch.empty((ks, T, RP), dtype=torch.float32, device=x2.device) for _ in range(G)]
-    flat = [a for Ag in A for a in Ag]
-    _lib.check(lib.moka_down_fwd_group(x2.data_ptr(), _ptrs(flat), rt.tok_mod.data_ptr(), _ptrs(parts),
-                                       T, d_in, r, M, G, float(s_in), float(dropout_p),
-                                       _u64s(seeds if seeds is not None else [0] * G), _lib.MOKA_BF16,
-                                       _det_opts(x2.device, T, d_in, r, G, M, seed_dev, want_det=False), _stream_ptr(x2.device)), "moka_down_fwd_group")
-    return parts
-
-
-def cross_fwd_group(parts: Sequence[torch.Tensor], rt: MokaRouting, r: int, s_out: Sequence[float], w: float, inv_sqrt_dk: float,
-                    Bw: Sequence[torch.Tensor], A: Optional[Sequence[Sequence[torch.Tensor]]] = None, want_tok: bool = True) -> List[FwdState]:
-    lib = _lib.load()
-    G = len(parts)
-    ks, T, RP = parts[0].shape
-    dev = parts[0].device
-    Tp = _lib.tok_pad(T)
-    sts = []
-    for g in range(G):
-        st = FwdState()
-        st.h = torch.empty((T, RP), dtype=torch.float32, device=dev)
-        st.hp = None
-        st.hp_tok = torch.empty((Tp, 2 * RP), dtype=torch.bfloat16, device=dev) if want_tok else None
-        st.hp_kmj = torch.empty((2, RP, Tp), dtype=torch.bfloat16, device=dev)
-        st.BwT = torch.empty((RP, Bw[g].shape[0]), dtype=torch.bfloat16, device=dev)
-        st.AT = torch.empty((len(A[g]), A[g][0].shape[1], RP), dtype=torch.bfloat16, device=dev) if A is not None else None
-        sts.append(st)
-    flatA = None if A is None else _ptrs([a for Ag in A for a in Ag])
-    _lib.check(lib.moka_cross_fwd_group(_ptrs(parts), ks, byref(rt.struct), _floats(s_out),
-                                        _ptrs(Bw), _ints([b.shape[0] for b in Bw]), flatA, 0 if A is None else A[0][0].shape[1],
-                                        _ptrs([st.h for st in sts]), None, _ptrs([st.hp_tok for st in sts]) if want_tok else None,
-                                        _ptrs([st.hp_kmj for st in sts]), _ptrs([st.BwT for st in sts]),
-                                        None if A is None else _ptrs([st.AT for st in sts]),
-                                        G, r, float(w), float(inv_sqrt_dk), _stream_ptr(dev)), "moka_cross_fwd_group")
-    return sts
-
-
-def up_fwd_group_(ys: Sequence[torch.Tensor], hp_toks: Sequence[torch.Tensor], Bw: Sequence[torch.Tensor], rt: MokaRouting, r: int):
-    lib = _lib.load()
-    T = ys[0].shape[0]
-    _lib.check(lib.moka_up_fwd_group(_ptrs(hp_toks), _ptrs(Bw), rt.tok_mod.data_ptr(), _ptrs(ys), T, r,
-                                     _ints([y.shape[1] for y in ys]), len(ys), _lib.MOKA_BF16, _stream_ptr(ys[0].device)),
-               "moka_up_fwd_group")
-
-
-def up_fwd_fused_group_(ys: Sequence[torch.Tensor], parts: Sequence[torch.Tensor], Bw: Sequence[torch.Tensor], rt: MokaRouting, r: int,
-                        s_out: Sequence[float], w: float, inv_sqrt_dk: float, want_state: bool = False) -> Optional[List[FwdState]]:
-    lib = _lib.load()
-    ks, T, RP = parts[0].shape
-    sts = None
-    if want_state:
-        sts = []
-        for _ in ys:
-            st = FwdState()
-            st.h = torch.empty((T, RP), dtype=torch.float32, device=parts[0].device)
-            st.hp_kmj = torch.empty((2, RP, _lib.tok_pad(T)), dtype=torch.bfloat16, device=parts[0].device)
-            st.hp = st.hp_tok = st.BwT = st.AT = None
-            sts.append(st)
-    _lib.check(lib.moka_up_fwd_fused_group(_ptrs(parts), ks, byref(rt.struct), _floats(s_out), _ptrs(Bw), _ptrs(ys),
-                                           _ints([y.shape[1] for y in ys]),
-                                           None if sts is None else _ptrs([st.h for st in sts]),
-                                           None if sts is None else _ptrs([st.hp_kmj for st in sts]),
-                                           len(ys), r, float(w), float(inv_sqrt_dk),
-                                           _lib.MOKA_BF16, _stream_ptr(ys[0].device)), "moka_up_fwd_fused_group")
-    return sts
-
-
-def weight_shadows_group(Bws: Sequence[torch.Tensor], As: Optional[Sequence[Sequence[torch.Tensor]]], r: int):
-    """Per projection (BwT, AT) of a group in one launch (AT only when `As` is given)."""
-    lib = _lib.load()
-    RP = _lib.rank_pad(r)
-    dev = Bws[0].device
-    G = len(Bws)
-    BwTs = [torch.empty((RP, b.shape[0]), dtype=torch.bfloat16, device=dev) for b in Bws]
-    ATs = [torch.empty((len(Ag), Ag[0].shape[1], RP), dtype=torch.bfloat16, device=dev) for Ag in As] if As is not None else None
-    M = len(As[0]) if As is not None else 1
-    _lib.check(lib.moka_weight_shadows_group(_ptrs(Bws), _ints([b.shape[0] for b in Bws]),
-                                             None if As is None else _ptrs([a for Ag in As for a in Ag]), 0 if As is None else As[0][0].shape[1],
-                                             _ptrs(BwTs), None if ATs is None else _ptrs(ATs), G, r, M, _stream_ptr(dev)),
-               "moka_weight_shadows_group")
-    return BwTs, ATs
-
-
-def up_bwd_group(gys: Sequence[torch.Tensor], hp_kmjs: Sequence[torch.Tensor], BwTs: Sequence[torch.Tensor], rt: MokaRouting, r: int,
-                 s_out: Sequence[float], dB_accs: Optional[Sequence[torch.Tensor]], want_g: bool = True) -> Optional[List[torch.Tensor]]:
+def up_bwd_group(gys: Sequence[torch.Tensor], hp_kmjs: Optional[Sequence[torch.Tensor]], BwTs: Optional[Sequence[torch.Tensor]],
+                 rt: MokaRouting, r: int, s_out: Sequence[float], dB_accs: Optional[Sequence[torch.Tensor]], want_g: bool = True,
+                 dtype: int = _lib.MOKA_BF16) -> Optional[List[torch.Tensor]]:
+    """gys[g] [T,d_out_g] -> g_parts[g] [ks,T,RP] (want_g=False: skip); dB_accs[g] [d_out_g,r] fp32 += (may be None: skip)."""
     lib = _lib.load()
     G = len(gys)
     T = gys[0].shape[0]
@@ -335,9 +219,9 @@ def up_bwd_group(gys: Sequence[torch.Tensor], hp_kmjs: Sequence[torch.Tensor], B
     d_outs = [g_.shape[1] for g_ in gys]
     ks = _lib.ksplit_bwd(T, max(d_outs), r)
     g_parts = [torch.empty((ks, T, RP), dtype=torch.float32, device=gys[0].device) for _ in range(G)] if want_g else None
-    _lib.check(lib.moka_up_bwd_group(_ptrs(gys), _ptrs(hp_kmjs), _ptrs(BwTs), rt.tok_mod.data_ptr(), _floats(s_out),
-                                     None if g_parts is None else _ptrs(g_parts), None if dB_accs is None else _ptrs(dB_accs),
-                                     T, r, _ints(d_outs), len(s_out), G, _lib.MOKA_BF16,
+    _lib.check(lib.moka_up_bwd_group(_ptrs(gys), _optptrs(hp_kmjs), _optptrs(BwTs), rt.tok_mod.data_ptr(), _floats(s_out),
+                                     _optptrs(g_parts), _optptrs(dB_accs),
+                                     T, r, _ints(d_outs), len(s_out), G, dtype,
                                      _det_opts(gys[0].device, T, max(d_outs), r, G, len(s_out)) if dB_accs is not None else None,
                                      _stream_ptr(gys[0].device)),
                "moka_up_bwd_group")
@@ -345,20 +229,14 @@ def up_bwd_group(gys: Sequence[torch.Tensor], hp_kmjs: Sequence[torch.Tensor], B
 
 
 def cross_bwd_group(g_parts: Sequence[torch.Tensor], hs: Sequence[torch.Tensor], rt: MokaRouting, r: int, s_in: float,
-                    w: float, inv_sqrt_dk: float) -> List[BwdState]:
+                    w: float, inv_sqrt_dk: float, want_dh: bool = False) -> List[BwdState]:
     lib = _lib.load()
     G = len(g_parts)
     ks, T, RP = g_parts[0].shape
     dev = g_parts[0].device
-    Tp = _lib.tok_pad(T)
-    sts = []
-    for g in range(G):
-        st = BwdState()
-        st.dh = None
-        st.dh_tok = torch.empty((Tp, 2 * RP), dtype=torch.bfloat16, device=dev)
-        st.dh_kmj = torch.empty((rt.M, 2, RP, Tp), dtype=torch.bfloat16, device=dev)
-        sts.append(st)
-    _lib.check(lib.moka_cross_bwd_group(_ptrs(g_parts), ks, _ptrs(hs), byref(rt.struct), float(s_in), None,
+    sts = [_bwd_state(T, RP, rt.M, dev, want_dh) for _ in range(G)]
+    _lib.check(lib.moka_cross_bwd_group(_ptrs(g_parts), ks, _ptrs(hs), byref(rt.struct), float(s_in),
+                                        _ptrs([st.dh for st in sts]) if want_dh else None,
                                         _ptrs([st.dh_tok for st in sts]), _ptrs([st.dh_kmj for st in sts]),
                                         _ptrs([rt.cross_ws(r, g) for g in range(G)]), G, r, float(w), float(inv_sqrt_dk),
                                         _stream_ptr(dev)), "moka_cross_bwd_group")
@@ -367,18 +245,71 @@ def cross_bwd_group(g_parts: Sequence[torch.Tensor], hs: Sequence[torch.Tensor],
 
 def down_bwd_group_(bsts: Sequence[BwdState], x2: torch.Tensor, ATs: Optional[Sequence[torch.Tensor]], rt: MokaRouting, r: int,
                     dA_accs: Optional[Sequence[Sequence[torch.Tensor]]], dx2: Optional[torch.Tensor],
-                    dropout_p: float = 0.0, seeds: Optional[Sequence[int]] = None, seed_dev: Optional[torch.Tensor] = None):
-    """dA_accs[g][m] += (one read of x2 for all G); dx2 += sum_g dh_g A_g (one read-modify-write)."""
+                    dropout_p: float = 0.0, seeds: Optional[Sequence[int]] = None, seed_dev: Optional[torch.Tensor] = None,
+                    dtype: int = _lib.MOKA_BF16):
+    """dA_accs[g][m] [r,d_in] fp32 += (one read of x2 for all G); dx2 [T,d_in] += sum_g dh_g A_g (one read-modify-write); either may be None."""
     lib = _lib.load()
     T, d_in = x2.shape
     G = len(bsts)
-    _lib.check(lib.moka_down_bwd_group(_ptrs([b.dh_tok for b in bsts]), _ptrs([b.dh_kmj for b in bsts]), x2.data_ptr(),
-                                       None if ATs is None else _ptrs(ATs), rt.tok_mod.data_ptr(),
+    _lib.check(lib.moka_down_bwd_group(_ptrs([b.dh_tok for b in bsts]), _optptrs([b.dh_kmj for b in bsts]), x2.data_ptr(),
+                                       _optptrs(ATs), rt.tok_mod.data_ptr(),
                                        None if dA_accs is None else _ptrs([a for Ag in dA_accs for a in Ag]),
                                        None if dx2 is None else dx2.data_ptr(), T, d_in, r, rt.M, G, float(dropout_p),
-                                       _u64s(seeds if seeds is not None else [0] * G), _lib.MOKA_BF16,
+                                       _u64s(seeds if seeds is not None else [0] * G), dtype,
                                        _det_opts(x2.device, T, d_in, r, G, rt.M, seed_dev, want_det=dA_accs is not None), _stream_ptr(x2.device)),
                "moka_down_bwd_group")
+
+
+# --------------------------------------------------------------------------------------
+# one projection: the same entry points as a group of one (as moka_X is moka_X_group(G = 1) in the library)
+# --------------------------------------------------------------------------------------
+def _one(t):
+    return None if t is None else [t]
+
+
+def down_fwd(x2: torch.Tensor, A: Sequence[torch.Tensor], rt: MokaRouting, r: int, s_in: float,
+             dropout_p: float = 0.0, seed: int = 0, dtype: int = 0, seed_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x2 [T,d_in] bf16 -> part [ks,T,RP] fp32 (split-K partials of s_in * drop(x) A_mod^T)."""
+    return down_fwd_group(x2, [A], rt, r, s_in, dropout_p, [seed], seed_dev, dtype)[0]
+
+
+def cross_fwd(part: torch.Tensor, rt: MokaRouting, r: int, s_out: Sequence[float], w: float, inv_sqrt_dk: float,
+              Bw: Optional[torch.Tensor] = None, want_hp: bool = False, A: Optional[Sequence[torch.Tensor]] = None,
+              want_tok: bool = True) -> FwdState:
+    return cross_fwd_group([part], rt, r, s_out, w, inv_sqrt_dk, _one(Bw), _one(A), want_tok, want_hp)[0]
+
+
+def up_fwd_fused_(y2: torch.Tensor, part: torch.Tensor, Bw: torch.Tensor, rt: MokaRouting, r: int, s_out: Sequence[float],
+                  w: float, inv_sqrt_dk: float, want_state: bool = False) -> Optional[FwdState]:
+    sts = up_fwd_fused_group_([y2], [part], [Bw], rt, r, s_out, w, inv_sqrt_dk, want_state)
+    return None if sts is None else sts[0]
+
+
+def weight_shadows(Bw: Optional[torch.Tensor], A: Optional[Sequence[torch.Tensor]], r: int) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    BwTs, ATs = weight_shadows_group(_one(Bw), _one(A), r)
+    return None if BwTs is None else BwTs[0], None if ATs is None else ATs[0]
+
+
+def up_fwd_(y2: torch.Tensor, hp_tok: torch.Tensor, Bw: torch.Tensor, rt: MokaRouting, r: int, dtype: int = 0):
+    up_fwd_group_([y2], [hp_tok], [Bw], rt, r, dtype)
+    return y2
+
+
+def up_bwd(gy2: torch.Tensor, hp_kmj: Optional[torch.Tensor], BwT: Optional[torch.Tensor], rt: MokaRouting, r: int,
+           s_out: Sequence[float], dB_acc: Optional[torch.Tensor], dtype: int = 0, want_g: bool = True) -> Optional[torch.Tensor]:
+    g_parts = up_bwd_group([gy2], _one(hp_kmj), _one(BwT), rt, r, s_out, _one(dB_acc), want_g, dtype)
+    return None if g_parts is None else g_parts[0]
+
+
+def cross_bwd(g_part: torch.Tensor, h: torch.Tensor, rt: MokaRouting, r: int, s_in: float, w: float, inv_sqrt_dk: float,
+              want_dh: bool = False) -> BwdState:
+    return cross_bwd_group([g_part], [h], rt, r, s_in, w, inv_sqrt_dk, want_dh)[0]
+
+
+def down_bwd_(bst: BwdState, x2: torch.Tensor, AT: Optional[torch.Tensor], rt: MokaRouting, r: int,
+              dA_acc: Optional[Sequence[torch.Tensor]], dx2: Optional[torch.Tensor],
+              dropout_p: float = 0.0, seed: int = 0, dtype: int = 0, seed_dev: Optional[torch.Tensor] = None):
+    down_bwd_group_([bst], x2, _one(AT), rt, r, _one(dA_acc), dx2, dropout_p, [seed], seed_dev, dtype)
 
 
 def down_bwd_da_batch_(dh_kmjs: Sequence[torch.Tensor], xs: Sequence[torch.Tensor], rt: MokaRouting, r: int,
@@ -519,13 +450,13 @@ def _split_like(flat: torch.Tensor, shapes: Sequence[Tuple[int, int]]) -> List[t
     return out
 
 
-# The forward of the autograd nodes: True (default) = moka_down_fwd -> moka_up_fwd_fused (+ moka_weight_shadows) where the fused launch
+# The forward of the autograd node: True (default) = moka_down_fwd -> moka_up_fwd_fused (+ moka_weight_shadows) where the fused launch
 # exists (bf16 storage) and pays for the shape (moka_up_fwd_fused_pays: not at rank pad 64); False = the three-launch path moka_down_fwd -> moka_cross_fwd -> moka_up_fwd.  Same bits either way
 # (tests/test_gpu_fused.py); a module-level switch for A/B runs, not a tuning knob.
 FUSE_FORWARD = True
 
 # Cached decode steps (masks None, no autograd, a handful of tokens): True = the base GEMMs + ONE moka_decode_fwd launch per
-# projection group (include/moka_decode.h: no split-K slices, no backward state, no weight shadows); False (default) = the autograd nodes
+# projection group (include/moka_decode.h: no split-K slices, no backward state, no weight shadows); False (default) = the autograd node
 # below, as for training.  A module-level switch for A/B runs (tools/decode_step.py), not a tuning knob.  It ships OFF: the kernel is
 # tested for correctness, but no timing of it against the general path is recorded yet ("Cached decode steps"); the
 # default turns on with that record.
@@ -544,7 +475,7 @@ def decode_serves(switch_on: bool, is_plain: bool, dtype: int, dropout_ps: Seque
 
 
 def _decode_forward(x, projections, rt: MokaRouting, specs):
-    """The outputs of a plain-routing call on the decode-step kernel, or None when the call belongs to the autograd nodes (which also
+    """The outputs of a plain-routing call on the decode-step kernel, or None when the call belongs to the autograd node (which also
     raise the errors of a malformed call).  Gathers the plain values of the call and asks ``decode_serves`` once.
 
     "Autograd records nothing" is judged per call, so a no-grad pass over TRAINABLE adapters is a decode call as well: under reentrant
@@ -581,7 +512,7 @@ def _decode_forward(x, projections, rt: MokaRouting, specs):
 
 
 # --------------------------------------------------------------------------------------
-# autograd node of one adapted projection
+# autograd node of 1..G adapted projections fed by the same x
 # --------------------------------------------------------------------------------------
 class AdapterSpec:
     """Static description of one adapted projection (what varies between AVT and VT)."""
@@ -612,168 +543,36 @@ class AdapterSpec:
 
 
 class MokaLinearFn(torch.autograd.Function):
-    """y = x W^T (+ bias) + adapter(x).  Inputs: x, W, bias|None, Bw, A_0..A_{M-1}.
+    """(y_0 .. y_{G-1}) = (x W_g^T (+ b_g) + adapter_g(x)) for the G >= 1 projections that read the same x: one projection, q/k/v of
+    the attention block, gate/up of the MLP.  x is read once by the G down-projections and once by the G dA kernels, and the G input
+    gradients are added to dx in one read-modify-write pass.
 
-    Forward: base GEMM (hipBLASLt through torch), then three launches -- down-projection,
-    cross-modal interaction, up-projection with the residual add done in place on the base
-    output.  Backward: base input-gradient GEMM (frozen W: no dW), then one pass over gy
-    (dL/dhp and dB), the rank-space backward, and one pass over x / dx (dA_m, dx += dh A_m).
-    Saves x, h and two small operand packs; the softmax is recomputed in rank space.
-    """
+    Inputs: x, rt, specs (list of G AdapterSpec: r / s_in / s_out / w / d_k / dropout_p must agree, seeds differ), G, M, then per
+    projection W_g, bias_g|None, Bw_g, A_g0..A_g{M-1}.  G = 1 only: fp32 storage, and W_0 = None (the adapter term alone).
 
-    @staticmethod
-    def forward(ctx, x, W, bias, Bw, rt: MokaRouting, spec: AdapterSpec, *A):
-        _require_device(x, "x")
-        dt = _storage([x, Bw, *A] + ([W] if W is not None else []), ["x", "lora_B"] + ["lora_A"] * len(A) + ["base weight"])
-        if len(spec.s_out) != rt.M or len(A) != rt.M:
-            raise ValueError(f"routing describes {rt.M} modalities but {len(A)} adapters / {len(spec.s_out)} scales were given")
-        d_in = x.shape[-1]
-        x2 = _dense(x.reshape(-1, d_in))
-        if x2.shape[0] != rt.T:
-            raise ValueError(f"x has {x2.shape[0]} tokens but the masks describe {rt.T}")
-        A = [_dense(a) for a in A]
-        Bw_c = _dense(Bw)
-        fused = (dt == _lib.MOKA_BF16 and FUSE_FORWARD and
-                 _lib.up_fwd_fused_pays(x2.shape[0], _lib.ksplit(x2.shape[0], d_in, spec.r), [Bw.shape[0]], spec.r, dt))
-        kept = spec.shadows if dt == _lib.MOKA_BF16 else None          # persistent (BwT, AT) of the weights' owner
-        if W is not None:
-            y = torch.nn.functional.linear(x2, W, bias)               # frozen base, stock PyTorch-ROCm
-        else:                                                         # adapter term alone (per-sample adapter_names: several adapters add to one base output)
-            y = torch.zeros((x2.shape[0], Bw.shape[0]), dtype=x2.dtype, device=x2.device)
-        part = down_fwd(x2, A, rt, spec.r, spec.s_in, spec.dropout_p, spec.seed, dtype=dt, seed_dev=spec.seed_dev)
-        if dt == _lib.MOKA_F32:
-            # fp32 storage: the rank-space rows themselves are the operands (no bf16 packs, no weight shadows)
-            st = cross_fwd(part, rt, spec.r, spec.s_out, spec.w, spec.inv_sqrt_dk, want_hp=True)
-            hps = st.hp * _token_scale(rt, spec.s_out, x2.device)[:, None]
-            up_fwd_(y, hps, Bw_c, rt, spec.r, dtype=dt)
-            ctx.save_for_backward(x2, W, Bw_c, st.h, hps, Bw_c, None, *A)
-        elif fused:
-            # two launches on the dependency chain: the up-projection computes the interaction itself from the slices and writes what
-            # the backward reads from the rank space (h, hp_kmj); the weight shadows are functions of the weights alone
-            st = up_fwd_fused_(y, part, Bw_c, rt, spec.r, spec.s_out, spec.w, spec.inv_sqrt_dk, want_state=True)
-            st.BwT, st.AT = kept if kept is not None else weight_shadows(Bw_c, A if ctx.needs_input_grad[0] else None, spec.r)
-            ctx.save_for_backward(x2, W, Bw_c, st.h, st.hp_kmj, st.BwT, st.AT, *A)
-        else:
-            if kept is not None:
-                st = cross_fwd(part, rt, spec.r, spec.s_out, spec.w, spec.inv_sqrt_dk)
-                st.BwT, st.AT = kept
-            else:
-                st = cross_fwd(part, rt, spec.r, spec.s_out, spec.w, spec.inv_sqrt_dk, Bw=Bw_c, A=A if ctx.needs_input_grad[0] else None)
-            up_fwd_(y, st.hp_tok, Bw_c, rt, spec.r)
-            ctx.save_for_backward(x2, W, Bw_c, st.h, st.hp_kmj, st.BwT, st.AT, *A)
-        ctx.rt, ctx.spec, ctx.x_shape, ctx.has_bias, ctx.dt = rt, spec, x.shape, bias is not None, dt
-        return y.reshape(*x.shape[:-1], y.shape[-1])
-
-    @staticmethod
-    def backward(ctx, gy):
-        x2, W, Bw, h, hp_kmj, BwT, AT, *A = ctx.saved_tensors
-        rt, spec = ctx.rt, ctx.spec
-        r = spec.r
-        gy2 = _dense(gy.reshape(-1, gy.shape[-1]))
-        need_x = ctx.needs_input_grad[0]
-        need_B = ctx.needs_input_grad[3]
-        need_A = any(ctx.needs_input_grad[6:])
-        if W is not None and ctx.needs_input_grad[1]:
-            raise _lib.MokaError("moka_amd: the base weight is frozen in MokA; requires_grad on it is not supported")
-        if spec.sinks is not None:
-            # the flat data-parallel gradient buffer is the accumulator (no temporaries, no cast, nothing returned to autograd)
-            dB_acc = spec.sinks[0] if need_B else None
-            dA_acc = list(spec.sinks[1]) if need_A else None
-            _check_sinks(dB_acc, dA_acc, Bw.shape[0], r, x2.shape[1], len(A), gy2.device)
-            if need_A:
-                # one launch fills the accumulators of ALL modalities: an A_m that asked for no gradient gets a scratch one, so that its
-                # sink (somebody else's slice of a flat buffer) keeps its bits
-                dA_acc = [t if ctx.needs_input_grad[6 + m] else torch.zeros_like(t) for m, t in enumerate(dA_acc)]
-            flat, shapes = None, []
-        else:
-            shapes = ([(Bw.shape[0], r)] if need_B else []) + ([(r, x2.shape[1])] * len(A) if need_A else [])
-            flat, acc = _grad_accumulators(shapes, gy2.device) if shapes else (None, [])
-            dB_acc = acc[0] if need_B else None
-            dA_acc = acc[(1 if need_B else 0):] if need_A else None
-        dt = ctx.dt
-        # dB is needed by the optimizer only: where it is a pass of its own over gy anyway (r > 32), it leaves the dependency chain like dA_m
-        split_dB = spec.sinks is not None and spec.defer is not None and dB_acc is not None and _lib.up_bwd_passes(r, dt) == 2
-        bst = None
-        g_part = up_bwd(gy2, hp_kmj, BwT, rt, r, spec.s_out, None if split_dB else dB_acc, dtype=dt)
-        if split_dB:
-            fn_db = lambda: up_bwd(gy2, hp_kmj, BwT, rt, r, spec.s_out, dB_acc, dtype=dt, want_g=False)   # noqa: E731
-            if dt == _lib.MOKA_BF16 and getattr(spec.defer, "accepts_da", False):
-                spec.defer(fn_db, [gy2, hp_kmj], db=((rt, r), [(gy2, hp_kmj, dB_acc)]))
-            else:
-                spec.defer(fn_db, [gy2, hp_kmj])
-        dx2 = None
-        if need_x:                                                   # frozen base: dx only, never dW
-            dx2 = torch.matmul(gy2, W) if W is not None else torch.zeros_like(x2)
-        if need_A or need_x:
-            if dt == _lib.MOKA_F32:
-                bst = cross_bwd(g_part, h, rt, r, spec.s_in, spec.w, spec.inv_sqrt_dk, want_dh=True)
-                bst.dh_tok, bst.dh_kmj = bst.dh * spec.s_in, None    # the fp32 rows, scaled, stand in for the packs
-                AT = torch.stack(list(A)).contiguous()
-            else:
-                bst = cross_bwd(g_part, h, rt, r, spec.s_in, spec.w, spec.inv_sqrt_dk)
-            if spec.sinks is not None and spec.defer is not None and dA_acc is not None:
-                if dx2 is not None:
-                    down_bwd_(bst, x2, AT, rt, r, None, dx2, spec.dropout_p, spec.seed, dtype=dt, seed_dev=spec.seed_dev)
-                fn = lambda bst=bst, x2=x2, AT=AT, dA_acc=dA_acc: down_bwd_(bst, x2, AT, rt, r, dA_acc, None, spec.dropout_p, spec.seed, dtype=dt, seed_dev=spec.seed_dev)   # noqa: E731
-                if dt == _lib.MOKA_BF16 and getattr(spec.defer, "accepts_da", False):
-                    # (described as well: attach() sends a decoder layer's dA_m halves out as ONE launch, moka_down_bwd_da_batch)
-                    spec.defer(fn, [x2, bst.dh_tok, bst.dh_kmj, AT], da=((rt, r, float(spec.dropout_p), spec.seed_dev), [(bst.dh_kmj, x2, list(dA_acc), spec.seed or 0)]))
-                else:
-                    spec.defer(fn, [x2, bst.dh_tok, bst.dh_kmj, AT])
-            else:
-                down_bwd_(bst, x2, AT, rt, r, dA_acc, dx2, spec.dropout_p, spec.seed, dtype=dt, seed_dev=spec.seed_dev)
-        gB, gA = None, [None] * len(A)
-        if flat is not None:
-            cast = _split_like(flat.to(Bw.dtype), shapes)             # one cast kernel for all weight gradients
-            if need_B:
-                gB = cast[0]
-            if need_A:
-                ca = cast[(1 if need_B else 0):]
-                gA = [ca[m] if ctx.needs_input_grad[6 + m] else None for m in range(len(A))]
-        gbias = gy2.sum(0) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
-        return (None if dx2 is None else dx2.reshape(ctx.x_shape), None, gbias, gB, None, None, *gA)
-
-
-def moka_linear(x, W, bias, Bw, A: Sequence[torch.Tensor], rt: MokaRouting, spec: AdapterSpec):
-    if getattr(rt, "dup_src", None) is not None:
-        # tokens of several modalities (MokaRouting.from_avt_masks): the adapter term over the real + virtual tokens, the virtual rows folded
-        # back onto the tokens they stand for (autograd carries their input gradients the same way); the frozen base sees the real tokens only
-        ya = rt.fold(MokaLinearFn.apply(rt.extend(x), None, None, Bw, rt, spec, *A)).reshape(*x.shape[:-1], Bw.shape[0])
-        return ya if W is None else torch.nn.functional.linear(x, W, bias) + ya
-    if getattr(rt, "is_plain", False):                   # mask-free call (masked training calls gather nothing for the decode rule): one launch behind the base GEMM where decode_serves says so
-        ys = _decode_forward(x, [(W, bias, Bw, A)], rt, [spec])
-        if ys is not None:
-            return ys[0]
-    return MokaLinearFn.apply(x, W, bias, Bw, rt, spec, *A)
-
-
-# --------------------------------------------------------------------------------------
-# autograd node of a GROUP of adapted projections fed by the same x (SURVEY.md 8(f1))
-# --------------------------------------------------------------------------------------
-class MokaLinearGroupFn(torch.autograd.Function):
-    """(y_0 .. y_{G-1}) = (x W_g^T (+ b_g) + adapter_g(x)) for the G projections that read the same x:
-    q/k/v of the attention block, gate/up of the MLP.  Same arithmetic as G MokaLinearFn nodes; x is
-    read once by the G down-projections and once by the G dA kernels, and the G input gradients are
-    added to dx in one read-modify-write pass.
-
-    Inputs: x, rt, specs (list of G AdapterSpec: r / s_in / s_out / w / d_k / dropout_p must agree, seeds
-    differ), G, M, then per projection W_g, bias_g|None, Bw_g, A_g0..A_g{M-1}.
+    Forward: base GEMMs (hipBLASLt through torch), then the down-projection and either the fused up-projection (+ the weight shadows)
+    or the cross-modal interaction and the up-projection, the residual add done in place on the base outputs.  Backward: base
+    input-gradient GEMMs (frozen W: no dW), then one pass over gy (dL/dhp and dB), the rank-space backward, and one pass over x / dx
+    (dA_m, dx += dh A_m).  Saves x, h and two small operand packs per projection; the softmax is recomputed in rank space.
     """
 
     @staticmethod
     def forward(ctx, x, rt: MokaRouting, specs, G: int, M: int, *flat):
         per = 3 + M
-        Ws = [flat[g * per] for g in range(G)]
-        biases = [flat[g * per + 1] for g in range(G)]
-        Bws = [flat[g * per + 2] for g in range(G)]
-        As = [list(flat[g * per + 3:g * per + 3 + M]) for g in range(G)]
+        Ws, biases, Bws = flat[0::per], flat[1::per], flat[2::per]
+        As = [flat[g * per + 3:(g + 1) * per] for g in range(G)]
         _require_device(x, "x")
-        _require_bf16(x, "x")
+        no_base = Ws[0] is None                                      # adapter term alone (per-sample adapter_names: several adapters add to one base output)
+        if G > 1 and any(W is None for W in Ws):
+            raise ValueError("moka_amd: a projection without a base weight (the adapter term alone) is a call of its own, not a member of a group")
+        ops, names = [x], ["x"]
         for g in range(G):
-            _require_bf16(Ws[g], "base weight")
-            _require_bf16(Bws[g], "lora_B")
-            for a in As[g]:
-                _require_bf16(a, "lora_A")
+            ops += [Bws[g], *As[g]] + ([] if no_base else [Ws[g]])
+            names += ["lora_B"] + ["lora_A"] * M + ["base weight"]
+        dt = _storage(ops, names)
+        bf16 = dt == _lib.MOKA_BF16
+        if G > 1 and not bf16:
+            raise _lib.MokaError("moka_amd: fp32 storage takes one projection per call (moka_linear_group sends them one at a time)")
         sp = specs[0]
         for o in specs[1:]:
             if (o.r, o.s_in, o.s_out, o.w, o.inv_sqrt_dk, o.dropout_p) != (sp.r, sp.s_in, sp.s_out, sp.w, sp.inv_sqrt_dk, sp.dropout_p) or o.seed_dev is not sp.seed_dev:
@@ -782,125 +581,148 @@ class MokaLinearGroupFn(torch.autograd.Function):
             raise ValueError(f"routing describes {rt.M} modalities but {M} adapters / {len(sp.s_out)} scales were given")
         d_in = x.shape[-1]
         x2 = _dense(x.reshape(-1, d_in))
-        if x2.shape[0] != rt.T:
-            raise ValueError(f"x has {x2.shape[0]} tokens but the masks describe {rt.T}")
+        T, r = x2.shape[0], sp.r
+        if T != rt.T:
+            raise ValueError(f"x has {T} tokens but the masks describe {rt.T}")
         As = [[_dense(a) for a in Ag] for Ag in As]
         Bws = [_dense(b) for b in Bws]
-        seeds = [s_.seed for s_ in specs]
         need_x = ctx.needs_input_grad[0]
-        fused = FUSE_FORWARD and _lib.up_fwd_fused_pays(x2.shape[0], _lib.ksplit(x2.shape[0], d_in, sp.r, len(Bws)), [b.shape[0] for b in Bws], sp.r)
-        kept = [s_.shadows for s_ in specs] if all(s_.shadows is not None for s_ in specs) else None     # persistent (BwT, AT) per projection
-        ys = [torch.nn.functional.linear(x2, Ws[g], biases[g]) for g in range(G)]      # frozen base, stock PyTorch-ROCm
-        parts = down_fwd_group(x2, As, rt, sp.r, sp.s_in, sp.dropout_p, seeds, seed_dev=sp.seed_dev)
-        if fused:
-            sts = up_fwd_fused_group_(ys, parts, Bws, rt, sp.r, sp.s_out, sp.w, sp.inv_sqrt_dk, want_state=True)     # (see MokaLinearFn.forward)
-            if kept is not None:
-                BwTs, ATs = [k[0] for k in kept], [k[1] for k in kept]
-            else:
-                BwTs, ATs = weight_shadows_group(Bws, As if need_x else None, sp.r)
-            for g in range(G):
-                sts[g].BwT, sts[g].AT = BwTs[g], (ATs[g] if ATs is not None else None)
+        fused = bf16 and FUSE_FORWARD and _lib.up_fwd_fused_pays(T, _lib.ksplit(T, d_in, r, G), [b.shape[0] for b in Bws], r, dt)
+        # persistent (BwT, AT) of the weights' owner, per projection: no launch is then asked for shadows, and none writes into these
+        kept = [o.shadows for o in specs] if bf16 and all(o.shadows is not None for o in specs) else None
+        if no_base:
+            ys = [torch.zeros((T, Bws[0].shape[0]), dtype=x2.dtype, device=x2.device)]
         else:
-            sts = cross_fwd_group(parts, rt, sp.r, sp.s_out, sp.w, sp.inv_sqrt_dk, Bws, As if need_x else None)
-            if kept is not None:
-                for g in range(G):
-                    sts[g].BwT, sts[g].AT = kept[g]
-            up_fwd_group_(ys, [st.hp_tok for st in sts], Bws, rt, sp.r)
+            ys = [torch.nn.functional.linear(x2, W, b) for W, b in zip(Ws, biases)]      # frozen base, stock PyTorch-ROCm
+        parts = down_fwd_group(x2, As, rt, r, sp.s_in, sp.dropout_p, [o.seed for o in specs], sp.seed_dev, dt)
+        if not bf16:
+            # fp32 storage: the rank-space rows themselves are the operands (no bf16 packs, no weight shadows)
+            sts = cross_fwd_group(parts, rt, r, sp.s_out, sp.w, sp.inv_sqrt_dk, want_hp=True)
+            hps = sts[0].hp * _token_scale(rt, sp.s_out, x2.device)[:, None]
+            up_fwd_group_(ys, [hps], Bws, rt, r, dt)
+            sts[0].hp_kmj, sts[0].BwT = hps, Bws[0]                  # what moka_up_bwd takes in their place
+        elif fused:
+            # two launches on the dependency chain: the up-projection computes the interaction itself from the slices and writes what
+            # the backward reads from the rank space (h, hp_kmj); the weight shadows are functions of the weights alone
+            sts = up_fwd_fused_group_(ys, parts, Bws, rt, r, sp.s_out, sp.w, sp.inv_sqrt_dk, want_state=True)
+            if kept is None:
+                BwTs, ATs = weight_shadows_group(Bws, As if need_x else None, r)
+                kept = list(zip(BwTs, ATs if ATs is not None else [None] * G))
+        else:
+            if kept is None:
+                sts = cross_fwd_group(parts, rt, r, sp.s_out, sp.w, sp.inv_sqrt_dk, Bws, As if need_x else None)
+            else:
+                sts = cross_fwd_group(parts, rt, r, sp.s_out, sp.w, sp.inv_sqrt_dk)
+            up_fwd_group_(ys, [st.hp_tok for st in sts], Bws, rt, r)
         saved = [x2]
-        for g in range(G):
-            saved += [Ws[g], Bws[g], sts[g].h, sts[g].hp_kmj, sts[g].BwT, sts[g].AT if need_x else None, *As[g]]
+        for g, st in enumerate(sts):
+            if kept is not None:
+                st.BwT, st.AT = kept[g]
+            saved += [Ws[g], Bws[g], st.h, st.hp_kmj, st.BwT, st.AT if need_x else None, *As[g]]
         ctx.save_for_backward(*saved)
-        ctx.rt, ctx.specs, ctx.G, ctx.M, ctx.x_shape = rt, specs, G, M, x.shape
+        ctx.rt, ctx.specs, ctx.G, ctx.M, ctx.x_shape, ctx.dt = rt, specs, G, M, x.shape, dt
         ctx.has_bias = [b is not None for b in biases]
         return tuple(y.reshape(*x.shape[:-1], y.shape[-1]) for y in ys)
 
     @staticmethod
     def backward(ctx, *gys):
-        G, M, rt, specs = ctx.G, ctx.M, ctx.rt, ctx.specs
+        G, M, rt, specs, dt = ctx.G, ctx.M, ctx.rt, ctx.specs, ctx.dt
         sp = specs[0]
         r = sp.r
-        saved = ctx.saved_tensors
-        x2 = saved[0]
+        x2, *saved = ctx.saved_tensors
         per_s = 6 + M
-        Ws = [saved[1 + g * per_s] for g in range(G)]
-        Bws = [saved[2 + g * per_s] for g in range(G)]
-        hs = [saved[3 + g * per_s] for g in range(G)]
-        hp_kmjs = [saved[4 + g * per_s] for g in range(G)]
-        BwTs = [saved[5 + g * per_s] for g in range(G)]
-        ATs = [saved[6 + g * per_s] for g in range(G)]
-        As = [list(saved[7 + g * per_s:7 + g * per_s + M]) for g in range(G)]
-        per = 3 + M
+        Ws, Bws, hs, hp_kmjs, BwTs, ATs = (saved[k::per_s] for k in range(6))
+        As = [saved[g * per_s + 6:(g + 1) * per_s] for g in range(G)]
         nig = ctx.needs_input_grad
-        base = 5                                                     # x, rt, specs, G, M
-        if any(nig[base + g * per] for g in range(G)):
+        per, base = 3 + M, 5                                         # x, rt, specs, G, M come first
+        if any(nig[base::per]):
             raise _lib.MokaError("moka_amd: the base weight is frozen in MokA; requires_grad on it is not supported")
         dev = x2.device
+        T, d_in = x2.shape
         gy2 = []
-        for g in range(G):
-            t_ = gys[g]
+        for g, t_ in enumerate(gys):
             if t_ is None:                                           # an output that did not reach the loss
-                t_ = torch.zeros((x2.shape[0], Ws[g].shape[0]), dtype=x2.dtype, device=dev)
-            t_ = t_.reshape(-1, t_.shape[-1])
-            gy2.append(_dense(t_))
+                t_ = torch.zeros((T, Bws[g].shape[0]), dtype=x2.dtype, device=dev)
+            gy2.append(_dense(t_.reshape(-1, t_.shape[-1])))
         need_x = nig[0]
-        need_B = any(nig[base + g * per + 2] for g in range(G))
-        need_A = any(nig[base + g * per + 3 + m] for g in range(G) for m in range(M))
-        use_sinks = all(s_.sinks is not None for s_ in specs)
+        on_B = nig[base + 2::per]                                    # per projection: lora_B asked for a gradient
+        on_A = [nig[base + g * per + 3:base + (g + 1) * per] for g in range(G)]
+        need_B, need_A = any(on_B), any(any(a) for a in on_A)
+        use_sinks = all(o.sinks is not None for o in specs)
         if use_sinks:
-            for g in range(G):
-                _check_sinks(specs[g].sinks[0] if need_B else None, list(specs[g].sinks[1]) if need_A else None,
-                             Bws[g].shape[0], r, x2.shape[1], M, dev)
+            # the flat data-parallel gradient buffer is the accumulator (no temporaries, no cast, nothing returned to autograd).  One
+            # launch fills the accumulators of the whole group and of ALL modalities: a parameter that asked for no gradient gets a
+            # scratch one, so that its sink (somebody else's slice of a flat buffer) keeps its bits
+            for g, o in enumerate(specs):
+                _check_sinks(o.sinks[0] if need_B else None, list(o.sinks[1]) if need_A else None, Bws[g].shape[0], r, d_in, M, dev)
             shapes, flat = [], None
-            # (one launch fills the accumulators of the whole group: a parameter that asked for no gradient gets a scratch one and its sink
-            #  keeps its bits -- see MokaLinearFn.backward)
-            acc = ([specs[g].sinks[0] if nig[base + g * per + 2] else torch.zeros_like(specs[g].sinks[0]) for g in range(G)] if need_B else []) + \
-                  ([a_ if nig[base + g * per + 3 + m] else torch.zeros_like(a_) for g in range(G) for m, a_ in enumerate(specs[g].sinks[1])] if need_A else [])
+            acc = ([o.sinks[0] if on_B[g] else torch.zeros_like(o.sinks[0]) for g, o in enumerate(specs)] if need_B else []) + \
+                  ([a_ if on_A[g][m] else torch.zeros_like(a_) for g, o in enumerate(specs) for m, a_ in enumerate(o.sinks[1])] if need_A else [])
         else:
-            shapes = ([(Bws[g].shape[0], r) for g in range(G)] if need_B else []) + ([(r, x2.shape[1])] * (G * M) if need_A else [])
+            shapes = ([(b.shape[0], r) for b in Bws] if need_B else []) + ([(r, d_in)] * (G * M) if need_A else [])
             flat, acc = _grad_accumulators(shapes, dev) if shapes else (None, [])
+        a0 = G if need_B else 0                                      # the accumulators are carved by what is needed: [dB_g ..] [dA_gm ..]
         dB_accs = acc[:G] if need_B else None
-        split_dB = use_sinks and sp.defer is not None and dB_accs is not None and _lib.up_bwd_passes(r, _lib.MOKA_BF16) == 2
-        bsts = None
-        g_parts = up_bwd_group(gy2, hp_kmjs, BwTs, rt, r, sp.s_out, None if split_dB else dB_accs)
-        if split_dB:                                                 # (see MokaLinearFn.backward)
-            fn_db = lambda: up_bwd_group(gy2, hp_kmjs, BwTs, rt, r, sp.s_out, dB_accs, want_g=False)   # noqa: E731
-            if getattr(sp.defer, "accepts_da", False):
-                sp.defer(fn_db, list(gy2) + list(hp_kmjs), db=((rt, r), [(gy2[g], hp_kmjs[g], dB_accs[g]) for g in range(G)]))
+        dA_accs = [acc[a0 + g * M:a0 + (g + 1) * M] for g in range(G)] if need_A else None
+        defer = sp.defer if use_sinks else None
+        described = dt == _lib.MOKA_BF16 and getattr(defer, "accepts_da", False)
+        # dB is needed by the optimizer only: where it is a pass of its own over gy anyway (r > 32), it leaves the dependency chain like dA_m
+        split_dB = defer is not None and dB_accs is not None and _lib.up_bwd_passes(r, dt) == 2
+        g_parts = up_bwd_group(gy2, hp_kmjs, BwTs, rt, r, sp.s_out, None if split_dB else dB_accs, dtype=dt)
+        if split_dB:
+            fn_db = lambda: up_bwd_group(gy2, hp_kmjs, BwTs, rt, r, sp.s_out, dB_accs, want_g=False, dtype=dt)   # noqa: E731
+            if described:
+                defer(fn_db, gy2 + list(hp_kmjs), db=((rt, r), list(zip(gy2, hp_kmjs, dB_accs))))
             else:
-                sp.defer(fn_db, list(gy2) + list(hp_kmjs))
+                defer(fn_db, gy2 + list(hp_kmjs))
         dx2 = None
-        if need_x:
-            dx2 = torch.matmul(gy2[0], Ws[0])                        # frozen base: dx only, never dW
+        if need_x:                                                   # frozen base: dx only, never dW
+            dx2 = torch.matmul(gy2[0], Ws[0]) if Ws[0] is not None else torch.zeros_like(x2)
             for g in range(1, G):
                 dx2.addmm_(gy2[g], Ws[g])
-        dA_accs = None
         if need_A or need_x:
-            if bsts is None:
-                bsts = cross_bwd_group(g_parts, hs, rt, r, sp.s_in, sp.w, sp.inv_sqrt_dk)
-            if need_A:
-                a0 = G if need_B else 0
-                dA_accs = [acc[a0 + g * M:a0 + (g + 1) * M] for g in range(G)]
-            seeds_ = [s_.seed for s_ in specs]
-            if use_sinks and sp.defer is not None and dA_accs is not None:
-                if dx2 is not None:
-                    down_bwd_group_(bsts, x2, ATs, rt, r, None, dx2, sp.dropout_p, seeds_, seed_dev=sp.seed_dev)
-                fn = lambda: down_bwd_group_(bsts, x2, None, rt, r, dA_accs, None, sp.dropout_p, seeds_, seed_dev=sp.seed_dev)   # noqa: E731
-                keep_ = [x2] + [b.dh_tok for b in bsts] + [b.dh_kmj for b in bsts]
-                if getattr(sp.defer, "accepts_da", False):
-                    sp.defer(fn, keep_, da=((rt, r, float(sp.dropout_p), sp.seed_dev), [(bsts[g].dh_kmj, x2, list(dA_accs[g]), seeds_[g] or 0) for g in range(G)]))
-                else:
-                    sp.defer(fn, keep_)
+            seeds = [o.seed for o in specs]
+            if dt == _lib.MOKA_F32:
+                bsts = cross_bwd_group(g_parts, hs, rt, r, sp.s_in, sp.w, sp.inv_sqrt_dk, want_dh=True)
+                bsts[0].dh_tok, bsts[0].dh_kmj = bsts[0].dh * sp.s_in, None    # the fp32 rows, scaled, stand in for the packs
+                ATs = AT_dA = [torch.stack(list(As[0])).contiguous()]           # ... and the stacked A_m for AT, which the fp32 entry point takes with every call
             else:
-                down_bwd_group_(bsts, x2, ATs if need_x else None, rt, r, dA_accs, dx2, sp.dropout_p, seeds_, seed_dev=sp.seed_dev)
-        cast = _split_like(flat.to(x2.dtype), shapes) if flat is not None else []      # one cast kernel for all weight gradients
+                bsts = cross_bwd_group(g_parts, hs, rt, r, sp.s_in, sp.w, sp.inv_sqrt_dk)
+                ATs, AT_dA = (ATs if need_x else None), None                   # bf16: the dx half alone reads AT
+            if defer is not None and dA_accs is not None:
+                if dx2 is not None:
+                    down_bwd_group_(bsts, x2, ATs, rt, r, None, dx2, sp.dropout_p, seeds, sp.seed_dev, dt)
+                fn = lambda: down_bwd_group_(bsts, x2, AT_dA, rt, r, dA_accs, None, sp.dropout_p, seeds, sp.seed_dev, dt)   # noqa: E731
+                keep = [x2] + [b.dh_tok for b in bsts] + [b.dh_kmj for b in bsts] + (AT_dA or [])
+                if described:
+                    # (described as well: attach() sends a decoder layer's dA_m halves out as ONE launch, moka_down_bwd_da_batch)
+                    defer(fn, keep, da=((rt, r, float(sp.dropout_p), sp.seed_dev),
+                                        [(bsts[g].dh_kmj, x2, list(dA_accs[g]), seeds[g] or 0) for g in range(G)]))
+                else:
+                    defer(fn, keep)
+            else:
+                down_bwd_group_(bsts, x2, ATs, rt, r, dA_accs, dx2, sp.dropout_p, seeds, sp.seed_dev, dt)
+        cast = _split_like(flat.to(x2.dtype), shapes) if flat is not None else None      # one cast kernel for all weight gradients
         grads = []
         for g in range(G):
             gbias = gy2[g].sum(0) if (ctx.has_bias[g] and nig[base + g * per + 1]) else None
-            gB = cast[g] if (cast and need_B and nig[base + g * per + 2]) else None
-            a0 = G if need_B else 0
-            gA = [cast[a0 + g * M + m] if (cast and need_A and nig[base + g * per + 3 + m]) else None for m in range(M)]
+            gB = cast[g] if (cast and on_B[g]) else None
+            gA = [cast[a0 + g * M + m] if (cast and on_A[g][m]) else None for m in range(M)]
             grads += [None, gbias, gB, *gA]
         return (None if dx2 is None else dx2.reshape(ctx.x_shape), None, None, None, None, *grads)
+
+
+def moka_linear(x, W, bias, Bw, A: Sequence[torch.Tensor], rt: MokaRouting, spec: AdapterSpec):
+    if getattr(rt, "dup_src", None) is not None:
+        # tokens of several modalities (MokaRouting.from_avt_masks): the adapter term over the real + virtual tokens, the virtual rows folded
+        # back onto the tokens they stand for (autograd carries their input gradients the same way); the frozen base sees the real tokens only
+        ya = rt.fold(MokaLinearFn.apply(rt.extend(x), rt, [spec], 1, len(A), None, None, Bw, *A)[0]).reshape(*x.shape[:-1], Bw.shape[0])
+        return ya if W is None else torch.nn.functional.linear(x, W, bias) + ya
+    if getattr(rt, "is_plain", False):                   # mask-free call (masked training calls gather nothing for the decode rule): one launch behind the base GEMM where decode_serves says so
+        ys = _decode_forward(x, [(W, bias, Bw, A)], rt, [spec])
+        if ys is not None:
+            return ys[0]
+    return MokaLinearFn.apply(x, rt, [spec], 1, len(A), W, bias, Bw, *A)[0]
 
 
 def moka_linear_group(x, projections, rt: MokaRouting, specs: Sequence[AdapterSpec]):
@@ -916,4 +738,4 @@ def moka_linear_group(x, projections, rt: MokaRouting, specs: Sequence[AdapterSp
     flat = []
     for W, b, Bw, A in projections:
         flat += [W, b, Bw, *A]
-    return list(MokaLinearGroupFn.apply(x, rt, list(specs), G, M, *flat))
+    return list(MokaLinearFn.apply(x, rt, list(specs), G, M, *flat))

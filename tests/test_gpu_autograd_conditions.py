@@ -1,4 +1,4 @@
-"""The two autograd nodes (moka_amd/functional.py: MokaLinearFn, MokaLinearGroupFn) against the fp64 oracle under the conditions a
+"""The autograd node (moka_amd/functional.py: MokaLinearFn, one projection or a group of G fed by the same x) against the fp64 oracle under the conditions a
 trainer creates and the other GPU files never do: partial ``requires_grad``, fp32 gradient sinks that already hold values,
 non-contiguous / offset / aliased inputs and upstream gradients, trainable bias, outputs that do not reach the loss, shared parameters,
 a retained graph, dropout -- and operands whose pointer is off the 16 bytes the kernels load at a time (include/moka_hip.h, "pointer
@@ -181,7 +181,7 @@ def _spec(spec0, **kw):
 # 1a. the requires_grad matrix
 # ==========================================================================================
 def _single(name, dt, x_on, B_on, A_on, use_sinks, base=False):
-    """One MokaLinearFn call + backward with the given requires_grad pattern.  Returns everything the checks need."""
+    """One moka_linear call + backward with the given requires_grad pattern.  Returns everything the checks need."""
     from moka_amd.functional import moka_linear
     dev = _dev()
     cd = _cd(name)
@@ -359,7 +359,7 @@ def _check_group(tag, name, G, res, x_on, flags, use_sinks, gy_none=()):
 @pytest.mark.parametrize("G", [2, 3])
 @pytest.mark.parametrize("name", CASES)
 def test_group_node_requires_grad_matrix(name, G, x_on, cfg, mode, fuse):
-    """MokaLinearGroupFn with gradients asked of ONE lora_B, of ONE lora_A_m, or of one whole projection only (x on and off): the
+    """MokaLinearFn on a group with gradients asked of ONE lora_B, of ONE lora_A_m, or of one whole projection only (x on and off): the
     accumulators are carved out of one flat buffer by what is needed, so every slice has to land on its own parameter."""
     flags = _group_flags(G, N_MOD[name], cfg)
     with _Fuse(fuse):
@@ -908,3 +908,100 @@ def test_c_abi_refuses_a_misaligned_pointer_before_launching_anything(entry, ope
     torch.cuda.synchronize()
     assert rc == 0, f"{entry}: rc={rc} {lib.moka_last_error().decode()}"
     assert not a.guard_damage()
+
+
+# ==========================================================================================
+# 1d. one node for 1..G projections: a group of one, kept shadows on the three-launch path, the refusal
+# ==========================================================================================
+def _grads_of(ys, x, projs):
+    return dict(y=[y.detach() for y in ys], dx=x.grad, dB=[p[2].grad for p in projs], dA=[[a.grad for a in p[3]] for p in projs])
+
+
+def _assert_same_run(tag, a, b):
+    for g, (ya, yb) in enumerate(zip(a["y"], b["y"])):
+        assert torch.equal(ya, yb), f"{tag}: y[{g}] differs"
+    assert torch.equal(a["dx"], b["dx"]), f"{tag}: dx differs"
+    for g, (ga, gb) in enumerate(zip(a["dB"], b["dB"])):
+        assert torch.equal(ga, gb), f"{tag}: dB[{g}] differs"
+    for g, (la, lb) in enumerate(zip(a["dA"], b["dA"])):
+        for m, (ga, gb) in enumerate(zip(la, lb)):
+            assert torch.equal(ga, gb), f"{tag}: dA[{g}][{m}] differs"
+
+
+def _group_of_one_vs_single(name, dt):
+    from moka_amd.functional import moka_linear, moka_linear_group
+    dev = _dev()
+    cd = _cd(name)
+    spec0, rt, _ = _srt(name)
+
+    def run(as_group):
+        x = _leaf(cd.x, dev, dt)
+        p = (cd.W.to(dev, dt), None, _leaf(cd.Bw, dev, dt), [_leaf(a, dev, dt) for a in cd.A])
+        spec = _spec(spec0, dropout_p=0.1, seed=0x5eed1 + cd.case.seed)
+        y = moka_linear_group(x, [p], rt, [spec])[0] if as_group else moka_linear(x, *p, rt, spec)
+        y.backward(cd.gy.to(dev, dt))
+        torch.cuda.synchronize()
+        return _grads_of([y], x, [p])
+
+    with _Det():
+        _assert_same_run(f"{name} {dt} group of one vs single", run(True), run(False))
+
+
+@pytest.mark.parametrize("fuse", [True, False], ids=["fused", "three_launch"])
+@pytest.mark.parametrize("name", CASES)
+def test_a_group_of_one_is_the_single_call(name, fuse):
+    """moka_linear_group(x, [p], rt, [spec]) and moka_linear(x, *p, rt, spec) on the same inputs, seed and dropout 0.1, deterministic
+    weight gradients: y, dx, dB and every dA_m are the same bits, with both forwards."""
+    with _Fuse(fuse):
+        _group_of_one_vs_single(name, bf)
+
+
+def test_a_group_of_one_is_the_single_call_fp32_storage():
+    """The same with fp32 storage: moka_linear_group sends fp32 calls to the node one projection at a time."""
+    _group_of_one_vs_single("avt_r8", f32)
+
+
+@pytest.mark.parametrize("G", [1, 3])
+@pytest.mark.parametrize("name", ["avt_r16_q", "avt_r64"], ids=["r16", "r64"])          # rank pads 16 and 64 (64 never takes the fused path)
+def test_kept_shadows_on_the_three_launch_path(name, G):
+    """spec.shadows = (BwT_g, AT_g) of weight_shadows_group for every member, three-launch forward: the same y, dx and (deterministic)
+    weight gradients as the call that computes its shadows, and the node writes neither into the shadows it was handed nor around them
+    (they sit in guard-banded buffers: every byte of the arena is what it was before the call)."""
+    from moka_amd import functional as F
+    dev = _dev()
+    cds, spec0, rt, _, _ = _group(name, 3)
+    cds = cds[:G]
+
+    def run(shadows):
+        x = _leaf(cds[0].x, dev)
+        projs = [(cd.W.to(dev, bf), None, _leaf(cd.Bw, dev), [_leaf(a, dev) for a in cd.A]) for cd in cds]
+        ys = F.moka_linear_group(x, projs, rt, [_spec(spec0, shadows=None if shadows is None else shadows[g]) for g in range(G)])
+        torch.autograd.backward(ys, [cd.gy.to(dev, bf) for cd in cds])
+        torch.cuda.synchronize()
+        return _grads_of(ys, x, projs)
+
+    BwTs, ATs = F.weight_shadows_group([cd.Bw.to(dev, bf) for cd in cds], [[a.to(dev, bf) for a in cd.A] for cd in cds], spec0.r)
+    bufs = {}
+    for g in range(G):
+        bufs[f"BwT{g}"] = Buf(tuple(BwTs[g].shape), bf, "input", data=BwTs[g])
+        bufs[f"AT{g}"] = Buf(tuple(ATs[g].shape), bf, "input", data=ATs[g])
+    arena = Arena(dev, bufs)
+    with _Fuse(False), _Det():
+        kept = run([(arena.view(f"BwT{g}"), arena.view(f"AT{g}")) for g in range(G)])
+        own = run(None)
+    _assert_same_run(f"{name} G={G} kept shadows vs computed", kept, own)
+    assert torch.equal(arena.mem, arena.before), f"{name} G={G}: the node wrote into or around the shadows it was handed"
+
+
+def test_a_group_member_without_a_base_weight_is_refused(monkeypatch):
+    """Two members, one with W = None (the adapter term alone is a call of its own): ValueError before any launch."""
+    from moka_amd import functional as F
+    dev = _dev()
+    cds, spec0, rt, _, _ = _group("avt_tiny", 2)
+    projs = [(cd.W.to(dev, bf) if g == 0 else None, None, _leaf(cd.Bw, dev), [_leaf(a, dev) for a in cd.A]) for g, cd in enumerate(cds)]
+    launches = []
+    check = F._lib.check
+    monkeypatch.setattr(F._lib, "check", lambda rc, what: (launches.append(what), check(rc, what))[1])
+    with pytest.raises(ValueError, match="base weight"):
+        F.moka_linear_group(_leaf(cds[0].x, dev), projs, rt, [_spec(spec0) for _ in cds])
+    assert launches == [], f"the refused call launched {launches}"
