@@ -2,7 +2,8 @@
 
     python -m moka_amd.build [--force] [--diag] [--unity]
 
-and of libmoka_decode.so, the decode-step kernel (csrc/moka_decode.hip, one translation unit), beside it.
+and of libmoka_decode.so, the decode-step kernel (csrc/moka_decode.hip, one translation unit), and libmoka_dlinear.so, the decode-step
+projection with the base GEMV inside (csrc/moka_dlinear.hip, one translation unit), beside it.
 
 The library is six translation units (moka_amd/csrc/k_*.hip: one per kernel family, moka_api.hip: the entry points and launch rules)
 compiled in parallel and linked; a change to the launch rules rebuilds in seconds, a change to one kernel family rebuilds that family.
@@ -27,6 +28,8 @@ OUT = os.path.join(HERE, "libmoka_hip.so")
 OUT_DIAG = os.path.join(HERE, "libmoka_hip_diag.so")       # -DMOKA_DIAGNOSTICS: moka_tune() launch-heuristic overrides (tools/ only)
 DECODE_SRC = os.path.join(CSRC, "moka_decode.hip")         # the decode-step kernel: a library of its own (include/moka_decode.h)
 OUT_DECODE = os.path.join(HERE, "libmoka_decode.so")
+DLINEAR_SRC = os.path.join(CSRC, "moka_dlinear.hip")       # base GEMV + adapter in one launch: a library of its own (include/moka_dlinear.h)
+OUT_DLINEAR = os.path.join(HERE, "libmoka_dlinear.so")
 INC = os.path.join(ROOT, "include")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-function", "-munsafe-fp-atomics", "-I", INC, "-I", CSRC]
 
@@ -74,12 +77,30 @@ def build_decode(force: bool = False, verbose: bool = True) -> str:
     return OUT_DECODE
 
 
+def dlinear_sources():
+    """Every file libmoka_dlinear.so is built from (kept apart from ``sources()`` and ``decode_sources()`` for the same reason)."""
+    return [DLINEAR_SRC, os.path.join(ROOT, "include", "moka_dlinear.h")] + HEADERS
+
+
+def build_dlinear(force: bool = False, verbose: bool = True) -> str:
+    """libmoka_dlinear.so (include/moka_dlinear.h): the decode-step projection, base GEMV and adapter in one launch; one translation
+    unit compiled and linked in one go."""
+    srcs = dlinear_sources()
+    if not force and os.path.exists(OUT_DLINEAR) and os.path.getmtime(OUT_DLINEAR) >= max(os.path.getmtime(p) for p in srcs):
+        return OUT_DLINEAR
+    _run([_hipcc()] + FLAGS + ["-shared", DLINEAR_SRC, "-o", OUT_DLINEAR + ".tmp"], verbose, "libmoka_dlinear.so")
+    os.replace(OUT_DLINEAR + ".tmp", OUT_DLINEAR)
+    return OUT_DLINEAR
+
+
 def build(force: bool = False, verbose: bool = True, diag: bool = False, unity: bool = False) -> str:
     """diag: the diagnostics variant (same ABI + working moka_tune), loaded by the tools through MOKA_HIP_LIB.  The product variant
-    also brings libmoka_decode.so up to date (``build_decode``); the path returned is libmoka_hip.so's."""
+    also brings libmoka_decode.so and libmoka_dlinear.so up to date (``build_decode``, ``build_dlinear``); the path returned is
+    libmoka_hip.so's."""
     out = OUT_DIAG if diag else OUT
     if not diag:
         build_decode(force=force, verbose=verbose)
+        build_dlinear(force=force, verbose=verbose)
     if not force and not needs_build(out):
         return out
     cc, defs = _hipcc(), (["-DMOKA_DIAGNOSTICS"] if diag else [])

@@ -15,7 +15,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-from . import _decode_lib, _lib
+from . import _decode_lib, _dlinear_lib, _lib
 from .routing import MokaRouting
 
 
@@ -474,6 +474,28 @@ def decode_serves(switch_on: bool, is_plain: bool, dtype: int, dropout_ps: Seque
     return _decode_lib.decode_ok(T, d_in, d_outs, r, dtype)
 
 
+# Cached decode steps of at most moka_dlinear_max_tokens (16) tokens: True = ONE moka_dlinear_fwd launch per projection group computes the
+# base GEMV, the bias and the adapter term (include/moka_dlinear.h: W is streamed once, y is rounded once, no torch.nn.functional.linear
+# call); False (default) = the paths below it, as DECODE_FORWARD says.  It is asked BEFORE DECODE_FORWARD and does not depend on it.  A
+# module-level switch for A/B runs (tools/decode_step.py, mode `fused`), not a tuning knob; it ships OFF and turns on, if at all, from
+# the record in DESIGN.md section 6.
+DLINEAR_FORWARD = False
+dlinear_launches = 0     # moka_dlinear_fwd calls made by moka_linear / moka_linear_group so far (tests and tools/decode_step.py read it)
+
+
+def dlinear_serves(switch_on: bool, is_plain: bool, dtype: int, dropout_ps: Sequence[float], grad_recorded: bool,
+                   T: int, d_in: int, d_outs: Sequence[int], r: int, weights_row_major: bool, biases_ok: bool) -> bool:
+    """Does the fused decode-step projection take this call?  Plain values in, as for ``decode_serves``: the switch is on, the routing is
+    ``MokaRouting.plain``, bf16 storage, no dropout, autograd records nothing, every base weight is a contiguous row-major
+    [d_out, d_in] matrix (not the transposed view of a ``fan_in_fan_out`` layer), every bias is absent or contiguous bf16, and the
+    library accepts the shape (moka_dlinear_ok: at most moka_dlinear_max_tokens tokens, at most three projections)."""
+    if not (switch_on and is_plain) or dtype != _lib.MOKA_BF16 or grad_recorded or any(p > 0.0 for p in dropout_ps):
+        return False
+    if not (weights_row_major and biases_ok):
+        return False
+    return _dlinear_lib.dlinear_ok(T, d_in, d_outs, r, dtype)
+
+
 def _decode_forward(x, projections, rt: MokaRouting, specs):
     """The outputs of a plain-routing call on the decode-step kernel, or None when the call belongs to the autograd node (which also
     raise the errors of a malformed call).  Gathers the plain values of the call and asks ``decode_serves`` once.
@@ -498,6 +520,24 @@ def _decode_forward(x, projections, rt: MokaRouting, specs):
         return None
     recorded = torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in tensors))
     d_outs = [int(Bw.shape[0]) for (_, _, Bw, _) in projections]
+    global dlinear_launches
+    if DLINEAR_FORWARD:                                                      # (off: nothing below is evaluated, the call is today's)
+        row_major = all(W.dim() == 2 and tuple(W.shape) == (d, d_in) and W.is_contiguous() and W.data_ptr() % 16 == 0
+                        for (W, _, _, _), d in zip(projections, d_outs))
+        biases_ok = all(b is None or (b.dtype == torch.bfloat16 and b.dim() == 1 and b.is_contiguous() and b.data_ptr() % 16 == 0)
+                        for (_, b, _, _) in projections)
+        if dlinear_serves(True, rt.is_plain, dtype, [o.dropout_p for o in specs], recorded, T, d_in, d_outs, sp.r, row_major, biases_ok):
+            x2 = _dense(x.reshape(-1, d_in))
+            ys = [torch.empty(T, d, dtype=x2.dtype, device=x2.device) for d in d_outs]             # written, never read
+            As = [_dense(A[0]) for (_, _, _, A) in projections]                                    # masks None: the text adapter alone
+            Bws = [_dense(Bw) for (_, _, Bw, _) in projections]
+            bs = [b for (_, b, _, _) in projections]
+            bias_arr = None if all(b is None for b in bs) else (c_void_p * len(bs))(*[None if b is None else b.data_ptr() for b in bs])
+            _dlinear_lib.check(_dlinear_lib.load().moka_dlinear_fwd(
+                x2.data_ptr(), _ptrs([W for (W, _, _, _) in projections]), bias_arr, _ptrs(As), _ptrs(Bws), _ptrs(ys), _ints(d_outs),
+                len(ys), T, d_in, sp.r, float(sp.s_in * sp.s_out[0]), _stream_ptr(x2.device)), "moka_dlinear_fwd")
+            dlinear_launches += 1
+            return [y.reshape(*x.shape[:-1], y.shape[-1]) for y in ys]
     if not decode_serves(DECODE_FORWARD, rt.is_plain, dtype, [o.dropout_p for o in specs], recorded, T, d_in, d_outs, sp.r):
         return None
     global decode_launches
