@@ -5,11 +5,10 @@ As there, NO fallback: a missing shared object raises ``MokaError``.
 """
 from __future__ import annotations
 
-import ctypes
 import os
 from ctypes import POINTER, c_char_p, c_float, c_int, c_void_p
 
-from ._lib import MOKA_BF16, MOKA_F32, MokaError   # noqa: F401  (the dtype codes are those of include/moka_hip.h)
+from ._lib import MOKA_BF16, MOKA_F32, MokaError, open_library   # noqa: F401  (the dtype codes are those of include/moka_hip.h)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmoka_decode.so")
@@ -32,19 +31,9 @@ SYMBOLS = {
 def load():
     """Load the shared library (once).  Raises MokaError when it has not been built."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise MokaError(
-            f"{LIB_PATH} not found: the decode-step HIP library has not been built "
-            "(run `python -c 'import __graft_entry__ as g; g.build()'`). moka_amd has no CPU / eager fallback.")
-    lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SYMBOLS.items():
-        fn = getattr(lib, name)          # AttributeError if the symbol is missing
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = open_library(LIB_PATH, SYMBOLS, "the decode-step HIP library")
+    return _lib
 
 
 def last_error() -> str:

@@ -138,20 +138,26 @@ SYMBOLS = {
 }
 
 
+def open_library(path: str, symbols, what: str):
+    """The shared object at ``path`` with every entry of a SYMBOLS table bound.  Raises MokaError when it has not been built."""
+    if not os.path.exists(path):
+        raise MokaError(
+            f"{path} not found: {what} has not been built "
+            "(run `python -c 'import __graft_entry__ as g; g.build()'`). moka_amd has no CPU / eager fallback.")
+    lib = ctypes.CDLL(path)
+    for name, (res, args) in symbols.items():
+        fn = getattr(lib, name)          # AttributeError if the symbol is missing
+        fn.restype = res
+        fn.argtypes = args
+    return lib
+
+
 def load():
     """Load the shared library (once).  Raises MokaError when it has not been built."""
     global _lib
     if _lib is not None:
         return _lib
-    if not os.path.exists(LIB_PATH):
-        raise MokaError(
-            f"{LIB_PATH} not found: the HIP extension has not been built "
-            "(run `python -c 'import __graft_entry__ as g; g.build()'`). moka_amd has no CPU / eager fallback.")
-    lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SYMBOLS.items():
-        fn = getattr(lib, name)          # AttributeError if the symbol is missing
-        fn.restype = res
-        fn.argtypes = args
+    lib = open_library(LIB_PATH, SYMBOLS, "the HIP extension")
     # MOKA_TUNE="key=value,key=value": launch-heuristic overrides (moka_tune) applied at load time -- lets bench.py and
     # the tests run unchanged under a different setting (diagnostics only; results never depend on it)
     for item in filter(None, os.environ.get("MOKA_TUNE", "").split(",")):

@@ -3,7 +3,7 @@
     python -m moka_amd.build [--force] [--diag] [--unity]
 
 and of libmoka_decode.so, the decode-step kernel (csrc/moka_decode.hip, one translation unit), and libmoka_dlinear.so, the decode-step
-projection with the base GEMV inside (csrc/moka_dlinear.hip, one translation unit), beside it.
+projection with the base GEMV inside (csrc/moka_dlinear.hip, one translation unit), beside it; the two share csrc/moka_step.h.
 
 The library is six translation units (moka_amd/csrc/k_*.hip: one per kernel family, moka_api.hip: the entry points and launch rules)
 compiled in parallel and linked; a change to the launch rules rebuilds in seconds, a change to one kernel family rebuilds that family.
@@ -30,6 +30,7 @@ DECODE_SRC = os.path.join(CSRC, "moka_decode.hip")         # the decode-step ker
 OUT_DECODE = os.path.join(HERE, "libmoka_decode.so")
 DLINEAR_SRC = os.path.join(CSRC, "moka_dlinear.hip")       # base GEMV + adapter in one launch: a library of its own (include/moka_dlinear.h)
 OUT_DLINEAR = os.path.join(HERE, "libmoka_dlinear.so")
+STEP_HDR = os.path.join(CSRC, "moka_step.h")               # what the two decode-step kernels share; no part of libmoka_hip.so
 INC = os.path.join(ROOT, "include")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-function", "-munsafe-fp-atomics", "-I", INC, "-I", CSRC]
 
@@ -64,33 +65,31 @@ def _run(cmd, verbose, what="libmoka_hip.so"):
 def decode_sources():
     """Every file libmoka_decode.so is built from.  Kept apart from ``sources()``: that list is what the traffic summaries of
     libmoka_hip.so are stamped with, and the decode kernel is no part of that library."""
-    return [DECODE_SRC, os.path.join(ROOT, "include", "moka_decode.h")] + HEADERS
-
-
-def build_decode(force: bool = False, verbose: bool = True) -> str:
-    """libmoka_decode.so (include/moka_decode.h): the decode-step adapter kernel, one translation unit compiled and linked in one go."""
-    srcs = decode_sources()
-    if not force and os.path.exists(OUT_DECODE) and os.path.getmtime(OUT_DECODE) >= max(os.path.getmtime(p) for p in srcs):
-        return OUT_DECODE
-    _run([_hipcc()] + FLAGS + ["-shared", DECODE_SRC, "-o", OUT_DECODE + ".tmp"], verbose, "libmoka_decode.so")
-    os.replace(OUT_DECODE + ".tmp", OUT_DECODE)
-    return OUT_DECODE
+    return [DECODE_SRC, STEP_HDR, os.path.join(ROOT, "include", "moka_decode.h")] + HEADERS
 
 
 def dlinear_sources():
     """Every file libmoka_dlinear.so is built from (kept apart from ``sources()`` and ``decode_sources()`` for the same reason)."""
-    return [DLINEAR_SRC, os.path.join(ROOT, "include", "moka_dlinear.h")] + HEADERS
+    return [DLINEAR_SRC, STEP_HDR, os.path.join(ROOT, "include", "moka_dlinear.h")] + HEADERS
+
+
+def _build_one(src: str, out: str, srcs, label: str, force: bool, verbose: bool) -> str:
+    """A library of one translation unit, compiled and linked in one go unless it is newer than everything it is built from."""
+    if not force and os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(p) for p in srcs):
+        return out
+    _run([_hipcc()] + FLAGS + ["-shared", src, "-o", out + ".tmp"], verbose, label)
+    os.replace(out + ".tmp", out)
+    return out
+
+
+def build_decode(force: bool = False, verbose: bool = True) -> str:
+    """libmoka_decode.so (include/moka_decode.h): the decode-step adapter kernel."""
+    return _build_one(DECODE_SRC, OUT_DECODE, decode_sources(), "libmoka_decode.so", force, verbose)
 
 
 def build_dlinear(force: bool = False, verbose: bool = True) -> str:
-    """libmoka_dlinear.so (include/moka_dlinear.h): the decode-step projection, base GEMV and adapter in one launch; one translation
-    unit compiled and linked in one go."""
-    srcs = dlinear_sources()
-    if not force and os.path.exists(OUT_DLINEAR) and os.path.getmtime(OUT_DLINEAR) >= max(os.path.getmtime(p) for p in srcs):
-        return OUT_DLINEAR
-    _run([_hipcc()] + FLAGS + ["-shared", DLINEAR_SRC, "-o", OUT_DLINEAR + ".tmp"], verbose, "libmoka_dlinear.so")
-    os.replace(OUT_DLINEAR + ".tmp", OUT_DLINEAR)
-    return OUT_DLINEAR
+    """libmoka_dlinear.so (include/moka_dlinear.h): the decode-step projection, base GEMV and adapter in one launch."""
+    return _build_one(DLINEAR_SRC, OUT_DLINEAR, dlinear_sources(), "libmoka_dlinear.so", force, verbose)
 
 
 def build(force: bool = False, verbose: bool = True, diag: bool = False, unity: bool = False) -> str:

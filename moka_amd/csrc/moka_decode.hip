@@ -16,20 +16,12 @@
 //             (RP / 16 MFMAs; rank pad 16: hi and lo share ONE instruction), 8-byte read-modify-write of y for tokens < T.
 // A lane of D holds one token and 4 consecutive columns, so rows >= T are simply not stored, and the duplicated rows the clamped loads
 // produced never reach memory.
-#include "moka_device.h"
+// The block map, the B-fragment load, the reduction tree, the split and the host-side shape checks are moka_step.h's, shared with
+// moka_dlinear.hip.
+#include "moka_step.h"
 #include "moka_decode.h"
 
 namespace {
-
-thread_local char g_derr[384] = "";
-
-int dfail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_derr, sizeof(g_derr), fmt, ap);
-    va_end(ap);
-    return code;
-}
 
 constexpr int DEC_NW = 8;             // waves per workgroup
 constexpr int DEC_CB_MIN = 64;        // output columns per workgroup, doubled until the launch has at most DEC_MAX_WG workgroups
@@ -51,18 +43,17 @@ struct DecodeArgs {
 // TT: 16-token tiles (T <= 16 TT), NT: 16-rank tiles (rank pad 16 NT)
 template <int TT, int NT>
 __global__ __launch_bounds__(64 * DEC_NW) void moka_decode_kernel(const DecodeArgs a) {
-    constexpr int RP = 16 * NT, NW = DEC_NW;
+    constexpr int NW = DEC_NW;
     constexpr int U = (TT + NT <= 2) ? 8 : ((TT + NT <= 4) ? 4 : 2);         // steps of loads in flight per wave
-    constexpr int HROW = 2 * RP + 8;                                          // bf16 per [hi | lo] row in LDS (16 bytes of padding)
-    constexpr int FR = TT * NT * 64;                                          // accumulator fragments of one wave
-    __shared__ f32x4 s_red[(NW / 2) * FR];                                    // (the [hi | lo] rows reuse it: TT (1024 NT + 256) bytes <= 4096 TT NT)
+    constexpr int HROW = step_hrow(NT);
+    constexpr int FR = TT * NT;                                               // accumulator fragments of one wave: f = tt * NT + nt
+    __shared__ f32x4 s_red[(NW / 2) * FR * 64];                               // (the [hi | lo] rows reuse it: TT (1024 NT + 256) bytes <= 4096 TT NT)
     unsigned short* const hs = (unsigned short*)s_red;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = lane & 15, g4 = lane >> 4;
-    const int bid = blockIdx.x;
-    const int g = (bid >= a.xend[0] ? 1 : 0) + (bid >= a.xend[1] ? 1 : 0);
-    const int cblk = bid - (g == 0 ? 0 : a.xend[g - 1]);
+    int g, cblk;
+    step_block(a.xend, blockIdx.x, g, cblk);
     const int C = a.C[g], r = a.r, T = a.T, d_in = a.d_in;
     const unsigned short* const Ag = a.A[g];
     const unsigned short* const Bg = a.Bw[g];
@@ -72,26 +63,9 @@ __global__ __launch_bounds__(64 * DEC_NW) void moka_decode_kernel(const DecodeAr
     // ---- phase 2 operands of the wave's first column tile: requested before phase 1, consumed behind it
     bf16x8 bfr[NT];
     u32x2 yv[TT];
-    const bool vecB = (r & 7) == 0;                                           // rows of B are whole 16-byte vectors
     auto load_tile = [&](int ct) {
         const int c0 = min(cblk * a.CB + 16 * ct, C - 16);                    // (a tile past C is never stored)
-        const unsigned short* brow = Bg + (size_t)(c0 + i) * r;
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            const int k0 = (32 * j + 8 * g4) & (RP - 1);                      // rank of this lane's contraction slots (rank pad 16: hi | lo in one step)
-            bf16x8 v;
-            if (vecB) {
-                v = *(const bf16x8*)(brow + min(k0, r - 8));
-                if (k0 >= r) v = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
-            } else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const unsigned short w = brow[min(k0 + e, r - 1)];
-                    v[e] = (k0 + e < r) ? (short)w : (short)0;
-                }
-            }
-            bfr[j] = v;
-        }
+        step_load_b<NT>(Bg + (size_t)(c0 + i) * r, r, g4, bfr);
 #pragma unroll
         for (int tt = 0; tt < TT; ++tt)
             yv[tt] = *(const u32x2*)(yg + (size_t)min(16 * tt + i, T - 1) * C + c0 + 4 * g4);
@@ -101,11 +75,9 @@ __global__ __launch_bounds__(64 * DEC_NW) void moka_decode_kernel(const DecodeAr
     load_tile(wave);
 
     // ---- phase 1: h^T[rank][token] = sum over this wave's 64-column steps
-    f32x4 acc[TT][NT];
+    f32x4 acc[FR];
 #pragma unroll
-    for (int tt = 0; tt < TT; ++tt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[tt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int f = 0; f < FR; ++f) acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
     {
         const unsigned short* xrow[TT];
         const unsigned short* arow[NT];
@@ -142,47 +114,18 @@ __global__ __launch_bounds__(64 * DEC_NW) void moka_decode_kernel(const DecodeAr
                     for (int tt = 0; tt < TT; ++tt) {
                         const bf16x8 xm = ok[u] ? xf[u][tt][h] : z8;          // branch-free: operands zeroed past d_in
 #pragma unroll
-                        for (int nt = 0; nt < NT; ++nt) acc[tt][nt] = MFMA16(ok[u] ? af[u][nt][h] : z8, xm, acc[tt][nt]);
+                        for (int nt = 0; nt < NT; ++nt) acc[tt * NT + nt] = MFMA16(ok[u] ? af[u][nt][h] : z8, xm, acc[tt * NT + nt]);
                     }
         }
     }
 
     // ---- the waves' partial sums: 8 -> 4 -> 2 -> 1 in a fixed order
-#pragma unroll
-    for (int tt = 0; tt < TT; ++tt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) MFMA_SETTLE(acc[tt][nt]);
-#pragma unroll
-    for (int half = NW / 2; half >= 1; half >>= 1) {
-        if (wave >= half && wave < 2 * half) {
-#pragma unroll
-            for (int f = 0; f < TT * NT; ++f) s_red[((wave - half) * TT * NT + f) * 64 + lane] = acc[f / NT][f % NT];
-        }
-        __syncthreads();
-        if (wave < half) {
-#pragma unroll
-            for (int f = 0; f < TT * NT; ++f) acc[f / NT][f % NT] += s_red[(wave * TT * NT + f) * 64 + lane];
-        }
-        __syncthreads();
-    }
+    step_wave_tree<NW>(acc, s_red, wave, lane);
 
     // ---- scale in fp32, split into hi + lo, token-major rows [hi(RP) | lo(RP)]; rank rows >= r are zero
     if (wave == 0) {
 #pragma unroll
-        for (int tt = 0; tt < TT; ++tt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                unsigned short hi[4], lo[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int k = 16 * nt + 4 * g4 + e;
-                    const float v = (k < r) ? a.scale * acc[tt][nt][e] : 0.f;
-                    split_hi_lo(v, hi[e], lo[e]);
-                }
-                unsigned short* row = hs + (size_t)(16 * tt + i) * HROW + 16 * nt + 4 * g4;
-                *(u32x2*)row = (u32x2){(unsigned)hi[0] | ((unsigned)hi[1] << 16), (unsigned)hi[2] | ((unsigned)hi[3] << 16)};
-                *(u32x2*)(row + RP) = (u32x2){(unsigned)lo[0] | ((unsigned)lo[1] << 16), (unsigned)lo[2] | ((unsigned)lo[3] << 16)};
-            }
+        for (int tt = 0; tt < TT; ++tt) step_split<NT>(acc, tt * NT, a.scale, r, hs, 16 * tt + i, g4);
     }
     __syncthreads();
 
@@ -220,29 +163,16 @@ void launch_nt(int NT, const DecodeArgs& a, unsigned blocks, hipStream_t st) {
     else hipLaunchKernelGGL((moka_decode_kernel<TT, 4>), grid, block, 0, st, a);
 }
 
-int dec_rank_pad(int r) { return (r < 1 || r > 64) ? MOKA_EINVAL : (r <= 16 ? 16 : (r <= 32 ? 32 : 64)); }
-
-// what no path accepts (the messages of include/moka_hip.h's entry points); T is judged by the callers
-int check_shape(const char* fn, int d_in, const int* d_out, int G, int r) {
-    if (G < 1 || G > MOKA_MAX_GROUP) return dfail(MOKA_EINVAL, "%s: G=%d not in 1..%d", fn, G, MOKA_MAX_GROUP);
-    if (!d_out) return dfail(MOKA_EINVAL, "%s: null pointer (d_out)", fn);
-    if (dec_rank_pad(r) < 0) return dfail(MOKA_EINVAL, "%s: rank %d not in 1..64", fn, r);
-    if (d_in < 32 || (d_in % 32) != 0) return dfail(MOKA_EINVAL, "%s: feature width %d must be a positive multiple of 32", fn, d_in);
-    for (int g = 0; g < G; ++g)
-        if (d_out[g] < 32 || (d_out[g] % 32) != 0) return dfail(MOKA_EINVAL, "%s: feature width %d must be a positive multiple of 32", fn, d_out[g]);
-    return MOKA_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
 int moka_decode_version(void) { return MOKA_DECODE_VERSION; }
-const char* moka_decode_last_error(void) { return g_derr; }
+const char* moka_decode_last_error(void) { return g_err; }
 int moka_decode_max_tokens(void) { return MOKA_DECODE_MAX_TOKENS; }
 
 int moka_decode_ok(int T, int d_in, const int* d_out, int G, int r, int dtype) {
-    if (dtype != MOKA_BF16 && dtype != MOKA_F32) return dfail(MOKA_EINVAL, "moka_decode_ok: storage dtype %d is neither MOKA_BF16 nor MOKA_F32", dtype);
+    if (dtype != MOKA_BF16 && dtype != MOKA_F32) return fail(MOKA_EINVAL, "moka_decode_ok: storage dtype %d is neither MOKA_BF16 nor MOKA_F32", dtype);
     const int rc = check_shape("moka_decode_ok", d_in, d_out, G, r);
     if (rc != MOKA_OK) return rc;
     if (dtype != MOKA_BF16) return 0;                                         // fp32 storage: the general path's exact-fp32 kernels
@@ -251,20 +181,19 @@ int moka_decode_ok(int T, int d_in, const int* d_out, int G, int r, int dtype) {
 
 int moka_decode_fwd(const void* x, const void* const* A, const void* const* Bw, void* const* y_inout, const int* d_out,
                     int G, int T, int d_in, int r, float scale, moka_stream_t stream) {
-    if (!x || !A || !Bw || !y_inout || !d_out) return dfail(MOKA_EINVAL, "moka_decode_fwd: null pointer");
+    if (!x || !A || !Bw || !y_inout || !d_out) return fail(MOKA_EINVAL, "moka_decode_fwd: null pointer");
     const int rc = check_shape("moka_decode_fwd", d_in, d_out, G, r);
     if (rc != MOKA_OK) return rc;
     if (T < 1 || T > MOKA_DECODE_MAX_TOKENS)
-        return dfail(MOKA_EINVAL, "moka_decode_fwd: T=%d not in 1..%d (moka_decode_max_tokens: use the general path)", T, MOKA_DECODE_MAX_TOKENS);
-    if ((uintptr_t)x & 15) return dfail(MOKA_EINVAL, "moka_decode_fwd: x must be 16-byte aligned");
+        return fail(MOKA_EINVAL, "moka_decode_fwd: T=%d not in 1..%d (moka_decode_max_tokens: use the general path)", T, MOKA_DECODE_MAX_TOKENS);
+    if ((uintptr_t)x & 15) return fail(MOKA_EINVAL, "moka_decode_fwd: x must be 16-byte aligned");
     DecodeArgs a;
     memset(&a, 0, sizeof(a));
     a.x = (const unsigned short*)x;
     a.T = T; a.d_in = d_in; a.r = r; a.scale = scale;
     for (int g = 0; g < G; ++g) {
-        if (!A[g] || !Bw[g] || !y_inout[g]) return dfail(MOKA_EINVAL, "moka_decode_fwd: null pointer (projection %d)", g);
-        if (((uintptr_t)A[g] | (uintptr_t)Bw[g] | (uintptr_t)y_inout[g]) & 15)
-            return dfail(MOKA_EINVAL, "moka_decode_fwd: A / Bw / y_inout of projection %d must be 16-byte aligned", g);
+        const int rcg = check_buffers("moka_decode_fwd", "A / Bw / y_inout", g, {A[g], Bw[g], y_inout[g]});
+        if (rcg != MOKA_OK) return rcg;
         a.A[g] = (const unsigned short*)A[g];
         a.Bw[g] = (const unsigned short*)Bw[g];
         a.y[g] = (unsigned short*)y_inout[g];
@@ -272,26 +201,18 @@ int moka_decode_fwd(const void* x, const void* const* A, const void* const* Bw, 
     }
     // launch rule: 64 columns per workgroup, doubled until the launch has at most one workgroup per CU
     int CB = DEC_CB_MIN;
-    long blocks;
-    for (;; CB *= 2) {
-        blocks = 0;
-        for (int g = 0; g < G; ++g) blocks += (d_out[g] + CB - 1) / CB;
-        if (blocks <= DEC_MAX_WG) break;
-    }
+    while (count_blocks(d_out, G, CB) > DEC_MAX_WG) CB *= 2;
+    const long blocks = count_blocks(d_out, G, CB);
     a.CB = CB;
-    int end = 0;
-    for (int g = 0; g < MOKA_MAX_GROUP; ++g) {
-        if (g < G) end += (d_out[g] + CB - 1) / CB;
-        a.xend[g] = end;                                                      // (absent projections: no block reaches them)
-    }
-    const int TT = (T + 15) >> 4, NT = dec_rank_pad(r) >> 4;
+    fill_xend(a.xend, d_out, G, CB);
+    const int TT = (T + 15) >> 4, NT = rank_pad(r) >> 4;
     const hipStream_t st = (hipStream_t)stream;
     if (TT == 1) launch_nt<1>(NT, a, (unsigned)blocks, st);
     else if (TT == 2) launch_nt<2>(NT, a, (unsigned)blocks, st);
     else if (TT == 3) launch_nt<3>(NT, a, (unsigned)blocks, st);
     else launch_nt<4>(NT, a, (unsigned)blocks, st);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return dfail(MOKA_ELAUNCH, "moka_decode_fwd: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(MOKA_ELAUNCH, "moka_decode_fwd: %s", hipGetErrorString(e));
     return MOKA_OK;
 }
 

@@ -21,20 +21,12 @@
 //             (the base sums are the MFMA's accumulator input), + bias in fp32, ONE rounding to bf16, 8-byte stores for tokens < T.
 // A lane of D holds one token and 4 consecutive columns, so rows >= T are simply not stored, and the duplicated rows the clamped loads
 // produced never reach memory.
-#include "moka_device.h"
+// The block map, the B-fragment load, the reduction tree, the split and the host-side shape checks are moka_step.h's, shared with
+// moka_decode.hip.
+#include "moka_step.h"
 #include "moka_dlinear.h"
 
 namespace {
-
-thread_local char g_lerr[384] = "";
-
-int lfail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_lerr, sizeof(g_lerr), fmt, ap);
-    va_end(ap);
-    return code;
-}
 
 constexpr int DL_NW = 8;              // waves per workgroup
 constexpr int DL_CB_START = 64;       // output columns per workgroup: the decode kernel's 64, doubled while the launch has more than DL_MAX_WG workgroups ...
@@ -62,9 +54,9 @@ struct DlinearArgs {
 // NTL: 16-column tiles of the workgroup's block (CB = 16 NTL), NT: 16-rank tiles (rank pad 16 NT)
 template <int NTL, int NT>
 __global__ __launch_bounds__(64 * DL_NW) void moka_dlinear_kernel(const DlinearArgs a) {
-    constexpr int RP = 16 * NT, NW = DL_NW, CB = 16 * NTL;
+    constexpr int NW = DL_NW, CB = 16 * NTL;
     constexpr int U = (NTL + NT <= 3) ? 4 : ((NTL + NT <= 8) ? 2 : 1);        // steps of loads in flight per wave (8 (1 + NT + NTL) registers each)
-    constexpr int HROW = 2 * RP + 8;                                          // bf16 per [hi | lo] row in LDS (16 bytes of padding)
+    constexpr int HROW = step_hrow(NT);
     constexpr int FR = NTL + NT;                                              // accumulator fragments of one wave: base tiles, then h tiles
     __shared__ f32x4 s_red[(NW / 2) * FR * 64];
     // after the tree: [0, NTL * 64) the base sums, behind them the [hi | lo] rows (1024 NTL + 32 HROW bytes <= 4096 (NTL + NT))
@@ -72,9 +64,8 @@ __global__ __launch_bounds__(64 * DL_NW) void moka_dlinear_kernel(const DlinearA
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = lane & 15, g4 = lane >> 4;
-    const int bid = blockIdx.x;
-    const int g = (bid >= a.xend[0] ? 1 : 0) + (bid >= a.xend[1] ? 1 : 0);
-    const int cblk = bid - (g == 0 ? 0 : a.xend[g - 1]);
+    int g, cblk;
+    step_block(a.xend, blockIdx.x, g, cblk);
     const int C = a.C[g], r = a.r, T = a.T, d_in = a.d_in;
     const unsigned short* const Ag = a.A[g];
     const unsigned short* const Bg = a.Bw[g];
@@ -88,27 +79,8 @@ __global__ __launch_bounds__(64 * DL_NW) void moka_dlinear_kernel(const DlinearA
     bf16x8 bfr[NT];
     u32x2 bv = {0u, 0u};
     const int c2 = min(cb0 + 16 * min(wave, NTL - 1), C - 16);
-    {
-        const bool vecB = (r & 7) == 0;                                       // rows of B are whole 16-byte vectors
-        const unsigned short* brow = Bg + (size_t)(c2 + i) * r;
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            const int k0 = (32 * j + 8 * g4) & (RP - 1);                      // rank of this lane's contraction slots (rank pad 16: hi | lo in one step)
-            bf16x8 v;
-            if (vecB) {
-                v = *(const bf16x8*)(brow + min(k0, r - 8));
-                if (k0 >= r) v = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
-            } else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const unsigned short w = brow[min(k0 + e, r - 1)];
-                    v[e] = (k0 + e < r) ? (short)w : (short)0;
-                }
-            }
-            bfr[j] = v;
-        }
-        if (bg) bv = *(const u32x2*)(bg + c2 + 4 * g4);                       // (wave uniform)
-    }
+    step_load_b<NT>(Bg + (size_t)(c2 + i) * r, r, g4, bfr);
+    if (bg) bv = *(const u32x2*)(bg + c2 + 4 * g4);                           // (wave uniform)
 
     // ---- phase 1: base^T[column][token] and h^T[rank][token], summed over this wave's 64-column steps
     f32x4 acc[FR];
@@ -159,39 +131,13 @@ __global__ __launch_bounds__(64 * DL_NW) void moka_dlinear_kernel(const DlinearA
     }
 
     // ---- the waves' partial sums: 8 -> 4 -> 2 -> 1 in a fixed order
-#pragma unroll
-    for (int f = 0; f < FR; ++f) MFMA_SETTLE(acc[f]);
-#pragma unroll
-    for (int half = NW / 2; half >= 1; half >>= 1) {
-        if (wave >= half && wave < 2 * half) {
-#pragma unroll
-            for (int f = 0; f < FR; ++f) s_red[((wave - half) * FR + f) * 64 + lane] = acc[f];
-        }
-        __syncthreads();
-        if (wave < half) {
-#pragma unroll
-            for (int f = 0; f < FR; ++f) acc[f] += s_red[(wave * FR + f) * 64 + lane];
-        }
-        __syncthreads();
-    }
+    step_wave_tree<NW>(acc, s_red, wave, lane);
 
     // ---- wave 0: the base sums as they are; h scaled in fp32 and split into hi + lo, token-major rows [hi(RP) | lo(RP)], rank rows >= r zero
     if (wave == 0) {
 #pragma unroll
         for (int ct = 0; ct < NTL; ++ct) s_red[ct * 64 + lane] = acc[ct];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            unsigned short hi[4], lo[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int k = 16 * nt + 4 * g4 + e;
-                const float v = (k < r) ? a.scale * acc[NTL + nt][e] : 0.f;
-                split_hi_lo(v, hi[e], lo[e]);
-            }
-            unsigned short* row = hs + (size_t)i * HROW + 16 * nt + 4 * g4;
-            *(u32x2*)row = (u32x2){(unsigned)hi[0] | ((unsigned)hi[1] << 16), (unsigned)hi[2] | ((unsigned)hi[3] << 16)};
-            *(u32x2*)(row + RP) = (u32x2){(unsigned)lo[0] | ((unsigned)lo[1] << 16), (unsigned)lo[2] | ((unsigned)lo[3] << 16)};
-        }
+        step_split<NT>(acc, NTL, a.scale, r, hs, i, g4);
     }
     __syncthreads();
 
@@ -217,25 +163,6 @@ void launch_nt(int NT, const DlinearArgs& a, unsigned blocks, hipStream_t st) {
     else hipLaunchKernelGGL((moka_dlinear_kernel<NTL, 4>), grid, block, 0, st, a);
 }
 
-int dl_rank_pad(int r) { return (r < 1 || r > 64) ? MOKA_EINVAL : (r <= 16 ? 16 : (r <= 32 ? 32 : 64)); }
-
-// what no path accepts (the messages of moka_decode.hip); T is judged by the callers
-int check_shape(const char* fn, int d_in, const int* d_out, int G, int r) {
-    if (G < 1 || G > MOKA_MAX_GROUP) return lfail(MOKA_EINVAL, "%s: G=%d not in 1..%d", fn, G, MOKA_MAX_GROUP);
-    if (!d_out) return lfail(MOKA_EINVAL, "%s: null pointer (d_out)", fn);
-    if (dl_rank_pad(r) < 0) return lfail(MOKA_EINVAL, "%s: rank %d not in 1..64", fn, r);
-    if (d_in < 32 || (d_in % 32) != 0) return lfail(MOKA_EINVAL, "%s: feature width %d must be a positive multiple of 32", fn, d_in);
-    for (int g = 0; g < G; ++g)
-        if (d_out[g] < 32 || (d_out[g] % 32) != 0) return lfail(MOKA_EINVAL, "%s: feature width %d must be a positive multiple of 32", fn, d_out[g]);
-    return MOKA_OK;
-}
-
-long count_blocks(const int* d_out, int G, int CB) {
-    long blocks = 0;
-    for (int g = 0; g < G; ++g) blocks += (d_out[g] + CB - 1) / CB;
-    return blocks;
-}
-
 // the launch rule: 64 columns per workgroup, doubled while the launch has more than one workgroup per CU and the block fits the
 // registers, halved while the halved launch still has at most one workgroup per CU
 long launch_rule(const int* d_out, int G, int* CB_out) {
@@ -251,11 +178,11 @@ long launch_rule(const int* d_out, int G, int* CB_out) {
 extern "C" {
 
 int moka_dlinear_version(void) { return MOKA_DLINEAR_VERSION; }
-const char* moka_dlinear_last_error(void) { return g_lerr; }
+const char* moka_dlinear_last_error(void) { return g_err; }
 int moka_dlinear_max_tokens(void) { return MOKA_DLINEAR_MAX_TOKENS; }
 
 int moka_dlinear_ok(int T, int d_in, const int* d_out, int G, int r, int dtype) {
-    if (dtype != MOKA_BF16 && dtype != MOKA_F32) return lfail(MOKA_EINVAL, "moka_dlinear_ok: storage dtype %d is neither MOKA_BF16 nor MOKA_F32", dtype);
+    if (dtype != MOKA_BF16 && dtype != MOKA_F32) return fail(MOKA_EINVAL, "moka_dlinear_ok: storage dtype %d is neither MOKA_BF16 nor MOKA_F32", dtype);
     const int rc = check_shape("moka_dlinear_ok", d_in, d_out, G, r);
     if (rc != MOKA_OK) return rc;
     if (dtype != MOKA_BF16) return 0;                                         // fp32 storage: the general path's exact-fp32 kernels
@@ -271,21 +198,20 @@ int moka_dlinear_workgroups(const int* d_out, int G, int d_in, int r) {
 
 int moka_dlinear_fwd(const void* x, const void* const* W, const void* const* bias, const void* const* A, const void* const* Bw,
                      void* const* y_out, const int* d_out, int G, int T, int d_in, int r, float scale, moka_stream_t stream) {
-    if (!x || !W || !A || !Bw || !y_out || !d_out) return lfail(MOKA_EINVAL, "moka_dlinear_fwd: null pointer");
+    if (!x || !W || !A || !Bw || !y_out || !d_out) return fail(MOKA_EINVAL, "moka_dlinear_fwd: null pointer");
     const int rc = check_shape("moka_dlinear_fwd", d_in, d_out, G, r);
     if (rc != MOKA_OK) return rc;
     if (T < 1 || T > MOKA_DLINEAR_MAX_TOKENS)
-        return lfail(MOKA_EINVAL, "moka_dlinear_fwd: T=%d not in 1..%d (moka_dlinear_max_tokens: the base GEMM belongs to the caller)", T, MOKA_DLINEAR_MAX_TOKENS);
-    if ((uintptr_t)x & 15) return lfail(MOKA_EINVAL, "moka_dlinear_fwd: x must be 16-byte aligned");
+        return fail(MOKA_EINVAL, "moka_dlinear_fwd: T=%d not in 1..%d (moka_dlinear_max_tokens: the base GEMM belongs to the caller)", T, MOKA_DLINEAR_MAX_TOKENS);
+    if ((uintptr_t)x & 15) return fail(MOKA_EINVAL, "moka_dlinear_fwd: x must be 16-byte aligned");
     DlinearArgs a;
     memset(&a, 0, sizeof(a));
     a.x = (const unsigned short*)x;
     a.T = T; a.d_in = d_in; a.r = r; a.scale = scale;
     for (int g = 0; g < G; ++g) {
         const void* b = bias ? bias[g] : nullptr;
-        if (!W[g] || !A[g] || !Bw[g] || !y_out[g]) return lfail(MOKA_EINVAL, "moka_dlinear_fwd: null pointer (projection %d)", g);
-        if (((uintptr_t)W[g] | (uintptr_t)A[g] | (uintptr_t)Bw[g] | (uintptr_t)y_out[g] | (uintptr_t)b) & 15)
-            return lfail(MOKA_EINVAL, "moka_dlinear_fwd: W / bias / A / Bw / y_out of projection %d must be 16-byte aligned", g);
+        const int rcg = check_buffers("moka_dlinear_fwd", "W / bias / A / Bw / y_out", g, {W[g], A[g], Bw[g], y_out[g]}, b);
+        if (rcg != MOKA_OK) return rcg;
         a.W[g] = (const unsigned short*)W[g];
         a.bias[g] = (const unsigned short*)b;
         a.A[g] = (const unsigned short*)A[g];
@@ -295,19 +221,15 @@ int moka_dlinear_fwd(const void* x, const void* const* W, const void* const* bia
     }
     int CB;
     const long blocks = launch_rule(d_out, G, &CB);
-    int end = 0;
-    for (int g = 0; g < MOKA_MAX_GROUP; ++g) {
-        if (g < G) end += (d_out[g] + CB - 1) / CB;
-        a.xend[g] = end;                                                      // (absent projections: no block reaches them)
-    }
-    const int NT = dl_rank_pad(r) >> 4;
+    fill_xend(a.xend, d_out, G, CB);
+    const int NT = rank_pad(r) >> 4;
     const hipStream_t st = (hipStream_t)stream;
     if (CB == 16) launch_nt<1>(NT, a, (unsigned)blocks, st);
     else if (CB == 32) launch_nt<2>(NT, a, (unsigned)blocks, st);
     else if (CB == 64) launch_nt<4>(NT, a, (unsigned)blocks, st);
     else launch_nt<8>(NT, a, (unsigned)blocks, st);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return lfail(MOKA_ELAUNCH, "moka_dlinear_fwd: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(MOKA_ELAUNCH, "moka_dlinear_fwd: %s", hipGetErrorString(e));
     return MOKA_OK;
 }
 

@@ -464,12 +464,17 @@ DECODE_FORWARD = False
 decode_launches = 0      # moka_decode_fwd calls made by moka_linear / moka_linear_group so far (tests and tools/decode_step.py read it)
 
 
+def _step_call(switch_on: bool, is_plain: bool, dtype: int, dropout_ps: Sequence[float], grad_recorded: bool) -> bool:
+    """What both decode-step libraries ask of a call before they look at its shape: their switch is on, the routing is
+    ``MokaRouting.plain``, bf16 storage, no dropout, autograd records nothing."""
+    return bool(switch_on and is_plain) and dtype == _lib.MOKA_BF16 and not grad_recorded and not any(p > 0.0 for p in dropout_ps)
+
+
 def decode_serves(switch_on: bool, is_plain: bool, dtype: int, dropout_ps: Sequence[float], grad_recorded: bool,
                   T: int, d_in: int, d_outs: Sequence[int], r: int) -> bool:
-    """Does the decode-step kernel take this call?  Plain values in, so the rule can be checked without a device: the switch is on, the
-    routing is ``MokaRouting.plain``, bf16 storage, no dropout, autograd records nothing, and the library accepts the shape
-    (moka_decode_ok: at most moka_decode_max_tokens tokens, at most three projections)."""
-    if not (switch_on and is_plain) or dtype != _lib.MOKA_BF16 or grad_recorded or any(p > 0.0 for p in dropout_ps):
+    """Does the decode-step kernel take this call?  Plain values in, so the rule can be checked without a device: ``_step_call``, and
+    the library accepts the shape (moka_decode_ok: at most moka_decode_max_tokens tokens, at most three projections)."""
+    if not _step_call(switch_on, is_plain, dtype, dropout_ps, grad_recorded):
         return False
     return _decode_lib.decode_ok(T, d_in, d_outs, r, dtype)
 
@@ -485,20 +490,19 @@ dlinear_launches = 0     # moka_dlinear_fwd calls made by moka_linear / moka_lin
 
 def dlinear_serves(switch_on: bool, is_plain: bool, dtype: int, dropout_ps: Sequence[float], grad_recorded: bool,
                    T: int, d_in: int, d_outs: Sequence[int], r: int, weights_row_major: bool, biases_ok: bool) -> bool:
-    """Does the fused decode-step projection take this call?  Plain values in, as for ``decode_serves``: the switch is on, the routing is
-    ``MokaRouting.plain``, bf16 storage, no dropout, autograd records nothing, every base weight is a contiguous row-major
-    [d_out, d_in] matrix (not the transposed view of a ``fan_in_fan_out`` layer), every bias is absent or contiguous bf16, and the
-    library accepts the shape (moka_dlinear_ok: at most moka_dlinear_max_tokens tokens, at most three projections)."""
-    if not (switch_on and is_plain) or dtype != _lib.MOKA_BF16 or grad_recorded or any(p > 0.0 for p in dropout_ps):
-        return False
-    if not (weights_row_major and biases_ok):
+    """Does the fused decode-step projection take this call?  Plain values in, as for ``decode_serves``: ``_step_call``, every base
+    weight is a contiguous row-major [d_out, d_in] matrix (not the transposed view of a ``fan_in_fan_out`` layer), every bias is absent
+    or contiguous bf16, and the library accepts the shape (moka_dlinear_ok: at most moka_dlinear_max_tokens tokens, at most three
+    projections)."""
+    if not (_step_call(switch_on, is_plain, dtype, dropout_ps, grad_recorded) and weights_row_major and biases_ok):
         return False
     return _dlinear_lib.dlinear_ok(T, d_in, d_outs, r, dtype)
 
 
 def _decode_forward(x, projections, rt: MokaRouting, specs):
     """The outputs of a plain-routing call on the decode-step kernel, or None when the call belongs to the autograd node (which also
-    raise the errors of a malformed call).  Gathers the plain values of the call and asks ``decode_serves`` once.
+    raise the errors of a malformed call).  Gathers the plain values of the call once, asks ``dlinear_serves`` where its switch is on, then
+    ``decode_serves``, and gathers the operands once for whichever library takes the call.
 
     "Autograd records nothing" is judged per call, so a no-grad pass over TRAINABLE adapters is a decode call as well: under reentrant
     activation checkpointing the first forward of a masks-None call of at most moka_decode_max_tokens tokens takes this kernel and the
@@ -520,34 +524,34 @@ def _decode_forward(x, projections, rt: MokaRouting, specs):
         return None
     recorded = torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in tensors))
     d_outs = [int(Bw.shape[0]) for (_, _, Bw, _) in projections]
-    global dlinear_launches
-    if DLINEAR_FORWARD:                                                      # (off: nothing below is evaluated, the call is today's)
+    dropout_ps = [o.dropout_p for o in specs]
+    fused = False
+    if DLINEAR_FORWARD:                                                      # (off: none of the layout checks is evaluated, the call is today's)
         row_major = all(W.dim() == 2 and tuple(W.shape) == (d, d_in) and W.is_contiguous() and W.data_ptr() % 16 == 0
                         for (W, _, _, _), d in zip(projections, d_outs))
         biases_ok = all(b is None or (b.dtype == torch.bfloat16 and b.dim() == 1 and b.is_contiguous() and b.data_ptr() % 16 == 0)
                         for (_, b, _, _) in projections)
-        if dlinear_serves(True, rt.is_plain, dtype, [o.dropout_p for o in specs], recorded, T, d_in, d_outs, sp.r, row_major, biases_ok):
-            x2 = _dense(x.reshape(-1, d_in))
-            ys = [torch.empty(T, d, dtype=x2.dtype, device=x2.device) for d in d_outs]             # written, never read
-            As = [_dense(A[0]) for (_, _, _, A) in projections]                                    # masks None: the text adapter alone
-            Bws = [_dense(Bw) for (_, _, Bw, _) in projections]
-            bs = [b for (_, b, _, _) in projections]
-            bias_arr = None if all(b is None for b in bs) else (c_void_p * len(bs))(*[None if b is None else b.data_ptr() for b in bs])
-            _dlinear_lib.check(_dlinear_lib.load().moka_dlinear_fwd(
-                x2.data_ptr(), _ptrs([W for (W, _, _, _) in projections]), bias_arr, _ptrs(As), _ptrs(Bws), _ptrs(ys), _ints(d_outs),
-                len(ys), T, d_in, sp.r, float(sp.s_in * sp.s_out[0]), _stream_ptr(x2.device)), "moka_dlinear_fwd")
-            dlinear_launches += 1
-            return [y.reshape(*x.shape[:-1], y.shape[-1]) for y in ys]
-    if not decode_serves(DECODE_FORWARD, rt.is_plain, dtype, [o.dropout_p for o in specs], recorded, T, d_in, d_outs, sp.r):
+        fused = dlinear_serves(True, rt.is_plain, dtype, dropout_ps, recorded, T, d_in, d_outs, sp.r, row_major, biases_ok)
+    if not fused and not decode_serves(DECODE_FORWARD, rt.is_plain, dtype, dropout_ps, recorded, T, d_in, d_outs, sp.r):
         return None
-    global decode_launches
+    global decode_launches, dlinear_launches
     x2 = _dense(x.reshape(-1, d_in))
-    ys = [_dense(torch.nn.functional.linear(x2, W, b)) for (W, b, _, _) in projections]      # frozen base, stock PyTorch-ROCm
     As = [_dense(A[0]) for (_, _, _, A) in projections]                                        # masks None: the text adapter alone
     Bws = [_dense(Bw) for (_, _, Bw, _) in projections]
-    _decode_lib.check(_decode_lib.load().moka_decode_fwd(x2.data_ptr(), _ptrs(As), _ptrs(Bws), _ptrs(ys), _ints(d_outs), len(ys), T, d_in,
-                                                         sp.r, float(sp.s_in * sp.s_out[0]), _stream_ptr(x2.device)), "moka_decode_fwd")
-    decode_launches += 1
+    scale, stream = float(sp.s_in * sp.s_out[0]), _stream_ptr(x2.device)
+    if fused:
+        ys = [torch.empty(T, d, dtype=x2.dtype, device=x2.device) for d in d_outs]             # written, never read
+        bs = [b for (_, b, _, _) in projections]
+        bias_arr = None if all(b is None for b in bs) else (c_void_p * len(bs))(*[None if b is None else b.data_ptr() for b in bs])
+        _dlinear_lib.check(_dlinear_lib.load().moka_dlinear_fwd(
+            x2.data_ptr(), _ptrs([W for (W, _, _, _) in projections]), bias_arr, _ptrs(As), _ptrs(Bws), _ptrs(ys), _ints(d_outs),
+            len(ys), T, d_in, sp.r, scale, stream), "moka_dlinear_fwd")
+        dlinear_launches += 1
+    else:
+        ys = [_dense(torch.nn.functional.linear(x2, W, b)) for (W, b, _, _) in projections]    # frozen base, stock PyTorch-ROCm
+        _decode_lib.check(_decode_lib.load().moka_decode_fwd(x2.data_ptr(), _ptrs(As), _ptrs(Bws), _ptrs(ys), _ints(d_outs), len(ys), T, d_in,
+                                                             sp.r, scale, stream), "moka_decode_fwd")
+        decode_launches += 1
     return [y.reshape(*x.shape[:-1], y.shape[-1]) for y in ys]
 
 

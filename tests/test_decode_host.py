@@ -2,12 +2,12 @@
 header declares, validates its arguments on the host, and the Python dispatch rule sends it exactly the calls it is meant for."""
 import ctypes
 import os
-import re
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.decode_util import ROOT, _declared, _ints
+
 BF16, F32 = 0, 1
 
 
@@ -17,16 +17,6 @@ def libs():
     path = build.build(verbose=False)          # hipcc cross-compiles without a GPU; no-op when up to date
     assert os.path.basename(path) == "libmoka_hip.so"
     return _lib.load(), _decode_lib.load()
-
-
-def _declared(header):
-    src = open(os.path.join(ROOT, "include", header)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(moka_[a-z_0-9]+)\s*\(", src)))
-
-
-def _ints(vals):
-    return (ctypes.c_int * len(vals))(*vals)
 
 
 def test_build_produces_both_libraries(libs):

@@ -3,11 +3,11 @@ without entering either, exports what its header declares, validates its argumen
 device, and the Python dispatch rule sends it exactly the calls it is meant for."""
 import ctypes
 import os
-import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.decode_util import ROOT, _declared, _ints
+
 BF16, F32 = 0, 1
 NAMES = ["moka_dlinear_fwd", "moka_dlinear_last_error", "moka_dlinear_max_tokens", "moka_dlinear_ok", "moka_dlinear_version",
          "moka_dlinear_workgroups"]
@@ -19,16 +19,6 @@ def libs():
     path = build.build(verbose=False)          # hipcc cross-compiles without a GPU; no-op when up to date
     assert os.path.basename(path) == "libmoka_hip.so"
     return _lib.load(), _decode_lib.load(), _dlinear_lib.load()
-
-
-def _declared(header):
-    src = open(os.path.join(ROOT, "include", header)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(moka_[a-z_0-9]+)\s*\(", src)))
-
-
-def _ints(vals):
-    return (ctypes.c_int * len(vals))(*vals)
 
 
 def test_build_produces_all_three_libraries(libs):
@@ -69,6 +59,16 @@ def test_the_other_libraries_hold_nothing_of_it(libs):
     assert build.UNITS == ["k_cross", "k_expand", "k_wgrad", "k_reduce", "k_misc", "moka_api"]
     assert [os.path.basename(h) for h in build.HEADERS] == ["moka_device.h", "moka_host.h", "moka_hip.h"]
     assert "dlinear" not in open(build.SRC).read()
+
+
+def test_the_shared_kernel_header_belongs_to_the_two_decode_libraries_alone():
+    from moka_amd import build
+    step = os.path.join(ROOT, "moka_amd", "csrc", "moka_step.h")
+    assert os.path.exists(step)
+    assert step in build.decode_sources() and step in build.dlinear_sources()         # both libraries rebuild when it changes
+    assert step not in build.sources()                                                # ... and the traffic stamp does not move
+    assert "decode" not in os.path.basename(step) and "dlinear" not in os.path.basename(step)
+    assert os.path.basename(step) not in open(build.SRC).read()                       # the unity file does not include it
 
 
 def test_dlinear_ok_table(libs):

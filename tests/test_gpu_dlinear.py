@@ -2,7 +2,6 @@
 one launch -- against the fp64 oracle and the two-step path it replaces, its buffer contract, its contractual properties (row /
 grouping independence, reproducibility), and the paths that reach it: the two PEFT mirrors, the decoder stack, a captured call -- and
 the calls that must NOT reach it."""
-import ctypes
 import math
 import random
 
@@ -12,11 +11,12 @@ import torch
 from oracle import cases as C
 from oracle import moka_oracle as O
 from tests.arena import Arena, Buf
+from tests.decode_util import (BF, _avt_masks, _avt_module, _dev, _mirror_call, _stack, _vt_module, decode_fwd, dlinear_fwd, rel,
+                               ulp_bf16_diff)
 from tests.golden_util import check_inputs, golden_rel_err, load_golden
 
 pytestmark = pytest.mark.gpu
 
-BF = torch.bfloat16
 TOL_BF16 = 1e-3            # tests/test_gpu_decode.py: a result against the oracle's value rounded to bf16
 TOL_E2E = 6e-3             # tests/test_gpu_decode.py: a mirror's output against the reference golden
 
@@ -29,55 +29,6 @@ def _switch_on():
     F.DLINEAR_FORWARD = True
     yield
     F.DLINEAR_FORWARD = saved
-
-
-def _dev():
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    return torch.device("cuda:0")
-
-
-def rel(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    n = b.norm().item()
-    d = (a - b).norm().item()
-    return d / n if n > 0 else d
-
-
-def ulp_bf16_diff(a_bf16, b_bf16, operand=None):
-    """max |a - b| in bf16 ulps, the measure of tests/test_gpu_decode.py: the ulp is taken at max(|b|, |operand|), elements below
-    rms / 256 are measured at that floor (the hi + lo split carries 2^-17 of each TERM)."""
-    a, b = a_bf16.float().cpu(), b_bf16.float().cpu()
-    mag = b.abs() if operand is None else torch.maximum(b.abs(), operand.float().cpu().abs().reshape(b.shape))
-    mag = mag.clamp_min(float(b.pow(2).mean().sqrt()) / 256)
-    ulp = torch.pow(2.0, torch.floor(torch.log2(mag.clamp_min(1e-30))) - 7)
-    return ((a - b).abs() / ulp).max().item()
-
-
-def _arr(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
-
-
-def dlinear_fwd(x, Ws, biases, As, Bs, ys, r, scale, T=None):
-    """moka_dlinear_fwd on raw tensors (x [T, d_in], W_g [d_out_g, d_in], bias_g [d_out_g] | None, A_g [r, d_in], B_g [d_out_g, r],
-    y_g [>= T, d_out_g] written)."""
-    from moka_amd import _dlinear_lib
-    lib = _dlinear_lib.load()
-    d_in = x.shape[1]
-    T = x.shape[0] if T is None else T
-    d_outs = (ctypes.c_int * len(ys))(*[y.shape[1] for y in ys])
-    barr = None if biases is None or all(b is None for b in biases) else _arr(biases)
-    rc = lib.moka_dlinear_fwd(x.data_ptr(), _arr(Ws), barr, _arr(As), _arr(Bs), _arr(ys), d_outs, len(ys), T, d_in, r, float(scale),
-                              ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-    assert rc == 0, _dlinear_lib.last_error()
-
-
-def decode_fwd(x, As, Bs, ys, r, scale):
-    from moka_amd import _decode_lib
-    T, d_in = x.shape
-    d_outs = (ctypes.c_int * len(ys))(*[y.shape[1] for y in ys])
-    rc = _decode_lib.load().moka_decode_fwd(x.data_ptr(), _arr(As), _arr(Bs), _arr(ys), d_outs, len(ys), T, d_in, r, float(scale),
-                                            ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-    assert rc == 0, _decode_lib.last_error()
 
 
 # ------------------------------------------------------------------------------------------ operands and the fp64 reference
@@ -266,43 +217,6 @@ def test_row_grouping_and_run_independence(d_in, d_outs, r, bias_mode):
 
 
 # ------------------------------------------------------------------------------------------ e. through the mirrors
-def _avt_module(cd, dev, p=0.0):
-    from moka_amd.peft_hyper import Linear
-    c = cd.case
-    lin = Linear(c.d_in, c.d_out, r=(c.r,) * 3, lora_alpha=c.alpha, lora_nums=3, blc_weight=c.w, blc_alpha=1, lora_dropout=p,
-                 loramethod="test", bias=False).to(dev, BF)
-    with torch.no_grad():
-        lin.weight.copy_(cd.W)
-        for i in range(len(cd.A)):
-            getattr(lin, f"lora_A{i}").weight.copy_(cd.A[i])
-        lin.lora_B0.weight.copy_(cd.Bw)
-    return lin
-
-
-def _vt_module(cd, dev, p=0.0, bias=False):
-    from moka_amd.modified_peft import Linear as VtLinear
-    c = cd.case
-    base = torch.nn.Linear(c.d_in, c.d_out, bias=bias)
-    base.weight.requires_grad_(False)                           # the frozen base
-    if bias:
-        base.bias.requires_grad_(False)
-    m = VtLinear(base, "image", r=c.r, lora_alpha=c.alpha, lora_dropout=p, attn_weight=c.w)
-    m.update_layer("text", c.r, lora_alpha=c.alpha, lora_dropout=p, init_lora_weights=True, use_rslora=False)
-    m.set_adapter(["image", "text"])
-    m = m.to(dev, BF)
-    with torch.no_grad():
-        m.get_base_layer().weight.copy_(cd.W)
-        m.lora_A["text"].weight.copy_(cd.A[0])
-        m.lora_B["text"].weight.copy_(cd.Bw)
-        if len(cd.A) > 1:
-            m.lora_A["image"].weight.copy_(cd.A[1])
-    return m
-
-
-def _mirror_call(kind, mod, x):
-    return mod(x, None) if kind == "avt" else mod(x, None, None, None)
-
-
 @pytest.mark.parametrize("decode_on", [False, True])
 @pytest.mark.parametrize("kind,name", [("avt", "avt_decode"), ("vt", "vt_none")])
 def test_mirrors_take_the_kernel_and_match_the_reference_golden(kind, name, decode_on, monkeypatch):
@@ -328,33 +242,6 @@ def test_mirrors_take_the_kernel_and_match_the_reference_golden(kind, name, deco
 
 
 # ------------------------------------------------------------------------------------------ f. through the decoder
-def _stack(dev, r=16, n_layers=2):
-    """The 2-layer stack of tests/test_gpu_decode.py::_stack."""
-    from moka_amd.decoder import LlamaDims, MokaLlamaStack
-    from moka_amd.peft_hyper import Linear
-    dims = LlamaDims(hidden=128, ff=352, n_heads=4, n_kv_heads=2)
-    torch.manual_seed(1)
-
-    def make(d_in, d_out):
-        m = Linear(d_in, d_out, r=(r, r, r), lora_alpha=16, lora_nums=3, blc_weight=1.0, blc_alpha=1, lora_dropout=0.0,
-                   loramethod="test", bias=False)
-        torch.nn.init.normal_(m.lora_B0.weight, std=0.05)
-        return m
-
-    return MokaLlamaStack(dims, n_layers, make).to(dev, BF).eval(), dims
-
-
-def _avt_masks(B, S, dev):
-    """[text, video, audio, question] int32 [B, S, 1]: 8 text, 24 video, 8 text, 16 audio, 12 question, rest text."""
-    tok = torch.zeros(S, dtype=torch.long)
-    tok[8:32] = 1
-    tok[40:56] = 2
-    q = torch.zeros(S, dtype=torch.int32)
-    q[56:68] = 1
-    ms = [(tok == m).to(torch.int32).reshape(1, S, 1).repeat(B, 1, 1).to(dev) for m in range(3)]
-    return ms + [q.reshape(1, S, 1).repeat(B, 1, 1).to(dev)]
-
-
 def test_decoder_steps_four_launches_per_layer():
     from moka_amd import functional as F
     dev = _dev()
