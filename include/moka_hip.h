@@ -17,8 +17,8 @@
  *     are owned by the caller.  Entry points are re-entrant and stateless (activation
  *     checkpointing re-runs the forward inside backward) and capture into hipGraphs as they are:
  *     the library keeps NO mutable state between calls -- per-call options travel in `moka_opts`
- *     (the deterministic-mode workspace), launch-heuristic overrides exist only in the
- *     diagnostics build (moka_tune).
+ *     (the deterministic-mode workspace); there are no launch-heuristic overrides (moka_tune
+ *     refuses: the diagnostics build that had them is gone).
  *   - token-major layouts: T = B*S flattened tokens, row-major, contiguous.
  *       x  [T, d_in]  bf16      y / gy [T, d_out] bf16      dx [T, d_in] bf16
  *       A_m [r, d_in] bf16 (lora_A{m}.weight / lora_A[name].weight)
@@ -153,11 +153,10 @@ const char* moka_last_error(void);
 /* 0 when a gfx950 device is current, MOKA_ENODEV otherwise. */
 int         moka_device_check(void);
 
-/* Diagnostics build only (-DMOKA_DIAGNOSTICS: `python -m moka_amd.build --diag` -> libmoka_hip_diag.so, loaded through
- * MOKA_HIP_LIB): override a launch heuristic ("expand_bpc", "expand_depth", "expand_nq", "wgrad_nw", "wgrad_ct", "wgrad_bpc",
- * "gy_ng", "xa_ng", "xa_form", "g32_fwd", "g32_dx", "g32_da", "g64_da", and the timing ablations "yx_dbg" / "gs_dbg" whose results are WRONG by design; value 0 restores the default).  Results never depend on it (set "xa_form" before sizing `part`:
- * moka_ksplit() follows it).  This is process-wide mutable state, which is why the PRODUCT library does not have it: there
- * moka_tune() returns MOKA_EINVAL and moka_diagnostics() returns 0. */
+/* Kept for ABI stability.  The launch-heuristic overrides these set lived in a diagnostics build of the library, which is gone (every
+ * sweep of them ended flat or worse than the defaults, and they were process-wide mutable state): moka_tune() always returns
+ * MOKA_EINVAL with a message that says so, moka_diagnostics() returns 0.  Two builds are compared by loading one or the other
+ * (MOKA_HIP_LIB in the Python package). */
 int moka_tune(const char* key, int value);
 int moka_diagnostics(void);
 
@@ -169,8 +168,8 @@ int moka_tok_pad(int T);
  * number of 256-column chunks per slice, chosen from T and the device's CU count so that the launch fills the chip -- at most one
  * per 256 columns, so C / 256 rounded up is an upper bound for any T).  `part` holds ks * T * RP floats. */
 int moka_ksplit(int T, int C, int r);
-/* The same for G (1..MOKA_MAX_GROUP) projections that share the input (moka_down_fwd_group): the slice width may depend on G (it does in
- * the diagnostics build's "xs_wide" experiment: 1024-column slices for a single projection at r <= 16); callers size `part` with this.
+/* The same for G (1..MOKA_MAX_GROUP) projections that share the input (moka_down_fwd_group): the slice width may depend on G (today it
+ * does not); callers size `part` with this.
  * moka_ksplit(T, C, r) == moka_ksplit_group(T, C, r, 1). */
 int moka_ksplit_group(int T, int C, int r, int G);
 /* Number of slices moka_up_bwd writes into g_part for output width C (= d_out; for a group: the largest

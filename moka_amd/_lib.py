@@ -158,8 +158,8 @@ def load():
     if _lib is not None:
         return _lib
     lib = open_library(LIB_PATH, SYMBOLS, "the HIP extension")
-    # MOKA_TUNE="key=value,key=value": launch-heuristic overrides (moka_tune) applied at load time -- lets bench.py and
-    # the tests run unchanged under a different setting (diagnostics only; results never depend on it)
+    # MOKA_TUNE="key=value,...": the launch-heuristic overrides of the former diagnostics build.  moka_tune() refuses them all, so a
+    # run that still sets the variable fails loudly here instead of measuring the defaults under another name.
     for item in filter(None, os.environ.get("MOKA_TUNE", "").split(",")):
         key, _, val = item.partition("=")
         if lib.moka_tune(key.strip().encode(), int(val)) != 0:

@@ -1,6 +1,6 @@
 """In-tree build of libmoka_hip.so for gfx950 (hipcc cross-compiles without a GPU).
 
-    python -m moka_amd.build [--force] [--diag] [--unity]
+    python -m moka_amd.build [--force] [--unity]
 
 and of libmoka_decode.so, the decode-step kernel (csrc/moka_decode.hip, one translation unit), and libmoka_dlinear.so, the decode-step
 projection with the base GEMV inside (csrc/moka_dlinear.hip, one translation unit), beside it; the two share csrc/moka_step.h.
@@ -25,7 +25,6 @@ UNITS = ["k_cross", "k_expand", "k_wgrad", "k_reduce", "k_misc", "moka_api"]
 HEADERS = [os.path.join(CSRC, "moka_device.h"), os.path.join(CSRC, "moka_host.h"), os.path.join(ROOT, "include", "moka_hip.h")]
 SRC = os.path.join(CSRC, "moka_kernels.hip")               # the unity form (tools/microbench/passlab.hip, tools/kernel_resources.sh)
 OUT = os.path.join(HERE, "libmoka_hip.so")
-OUT_DIAG = os.path.join(HERE, "libmoka_hip_diag.so")       # -DMOKA_DIAGNOSTICS: moka_tune() launch-heuristic overrides (tools/ only)
 DECODE_SRC = os.path.join(CSRC, "moka_decode.hip")         # the decode-step kernel: a library of its own (include/moka_decode.h)
 OUT_DECODE = os.path.join(HERE, "libmoka_decode.so")
 DLINEAR_SRC = os.path.join(CSRC, "moka_dlinear.hip")       # base GEMV + adapter in one launch: a library of its own (include/moka_dlinear.h)
@@ -92,29 +91,27 @@ def build_dlinear(force: bool = False, verbose: bool = True) -> str:
     return _build_one(DLINEAR_SRC, OUT_DLINEAR, dlinear_sources(), "libmoka_dlinear.so", force, verbose)
 
 
-def build(force: bool = False, verbose: bool = True, diag: bool = False, unity: bool = False) -> str:
-    """diag: the diagnostics variant (same ABI + working moka_tune), loaded by the tools through MOKA_HIP_LIB.  The product variant
-    also brings libmoka_decode.so and libmoka_dlinear.so up to date (``build_decode``, ``build_dlinear``); the path returned is
+def build(force: bool = False, verbose: bool = True, unity: bool = False) -> str:
+    """Also brings libmoka_decode.so and libmoka_dlinear.so up to date (``build_decode``, ``build_dlinear``); the path returned is
     libmoka_hip.so's."""
-    out = OUT_DIAG if diag else OUT
-    if not diag:
-        build_decode(force=force, verbose=verbose)
-        build_dlinear(force=force, verbose=verbose)
+    out = OUT
+    build_decode(force=force, verbose=verbose)
+    build_dlinear(force=force, verbose=verbose)
     if not force and not needs_build(out):
         return out
-    cc, defs = _hipcc(), (["-DMOKA_DIAGNOSTICS"] if diag else [])
+    cc = _hipcc()
     if unity:
-        _run([cc] + FLAGS + defs + ["-shared", SRC, "-o", out + ".tmp"], verbose)
+        _run([cc] + FLAGS + ["-shared", SRC, "-o", out + ".tmp"], verbose)
         os.replace(out + ".tmp", out)
         return out
-    objdir = os.path.join(CSRC, "_obj", "diag" if diag else "prod")
+    objdir = os.path.join(CSRC, "_obj")
     os.makedirs(objdir, exist_ok=True)
     newest_hdr = max(os.path.getmtime(h) for h in HEADERS)
     jobs = []
     for u in UNITS:
         src, obj = os.path.join(CSRC, u + ".hip"), os.path.join(objdir, u + ".o")
         if force or not os.path.exists(obj) or os.path.getmtime(obj) < max(os.path.getmtime(src), newest_hdr):
-            jobs.append([cc] + FLAGS + defs + ["-c", src, "-o", obj])
+            jobs.append([cc] + FLAGS + ["-c", src, "-o", obj])
     with concurrent.futures.ThreadPoolExecutor(max_workers=max(1, min(len(jobs) or 1, os.cpu_count() or 1))) as ex:
         list(ex.map(lambda c: _run(c, verbose), jobs))
     _run([cc, "--offload-arch=gfx950", "-shared", "-fPIC"] + [os.path.join(objdir, u + ".o") for u in UNITS] + ["-o", out + ".tmp"], verbose)
@@ -123,4 +120,4 @@ def build(force: bool = False, verbose: bool = True, diag: bool = False, unity: 
 
 
 if __name__ == "__main__":
-    print(build(force="--force" in sys.argv, diag="--diag" in sys.argv, unity="--unity" in sys.argv))
+    print(build(force="--force" in sys.argv, unity="--unity" in sys.argv))

@@ -17,11 +17,12 @@
 // for the whole block, other modalities' fragments are fetched from L2 for the (few) tiles that need them.
 // G > 1 (dx only): G projections read the same x (q/k/v, gate/up), so their input gradients land in the
 // same dx: one read-modify-write pass adds all G terms (each through its own dropout mask).
-template <int RP, int NQ, bool W_CK, int G, int DEPTH, bool RUNS>
+template <int RP, int NQ, bool W_CK, int G, bool RUNS>
 __global__ void __launch_bounds__(256) moka_expand_kernel(const ExpandBatch ab) {
     constexpr int KH = (RP + 31) / 32;                 // 32-wide rank blocks per hi (or lo) plane
     constexpr int WC = NQ * 32;                        // columns per wave
     constexpr int CW = 4 * WC;                         // columns per block
+    constexpr int DEPTH = 2;                           // token tiles in flight per wave (measured: 3-4 deep rings gain nothing once loads and stores are unconditional)
     // G == 1: batched problems share the x dimension of the grid (a problem narrower than the widest one would otherwise leave most
     // of its grid row as blocks that exit at once, and launching those is not free: 2900 of them cost the 70B q+k+v launch 60 us)
     // (problems of one width keep a grid row each, blockIdx.z: measured 1 % faster on the q/k/v launch of the 7B widths)
@@ -332,172 +333,7 @@ __global__ void __launch_bounds__(256) moka_expand_kernel(const ExpandBatch ab) 
 }
 
 // ------------------------------------------------------------------------------------------
-// E (rank pad 64, G > 1): dx += sum_g mask_g o (dh_g . A_g,m(t))  in ONE read-modify-write pass over dx.
-// The per-wave-resident weights of moka_expand_kernel do not fit three projections at this rank (250 registers, one wave per SIMD: it
-// lost), so the roles are turned round: a workgroup (8 waves) keeps 128 TOKENS -- wave w the 16-token tile w, its G x (hi, lo) pack
-// rows resident as MFMA B fragments (48 registers) -- and walks the columns in chunks of 128; the chunk's weights of all G projections
-// (G x 16 KB of A^T in fragment order) are staged in LDS for the eight waves, requested from L2 one step ahead into registers
-// (the moka_xwm_kernel scheme).  One walk step per (chunk, modality of the token run): every token is multiplied with the
-// staged modality's weights and the result counts only for the tokens OF that modality (selected on the output, tokens are MFMA
-// columns); then each projection's product passes its own dropout mask and joins the sum, and the dx tile is written once per chunk.
-// q/k/v (gate/up) cost one pass over dx instead of three (two).
-// ------------------------------------------------------------------------------------------
-template <int RP, int G>
-__global__ void __launch_bounds__(512, 2) moka_dxg_kernel(const ExpandBatch ab, int chunks_per_block) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int KH = (RP + 31) / 32, NQ = 4, CWK = NQ * 32, NF = NQ * 2 * KH;   // 8 KH fragments (1 KB each) per projection and chunk
-    constexpr int PER = G * NF * 64 / 512, PG = NF * 64 / 512;               // fragments per thread and step: PG (= KH) per projection
-    bf16x8* wl = (bf16x8*)smem;                                              // [G][NQ][2][KH][64]
-    __shared__ unsigned s_wpm[8];
-    const ExpandArgs& a = ab.z[0];
-    const uint2 ep = drop_epoch(a.drop);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i = lane & 15, g = lane >> 4;
-    const int ntiles = (a.T + 15) >> 4;
-    const int tile = blockIdx.y * 8 + wave;
-    const bool live = tile < ntiles;
-    const int t = min((min(tile, ntiles - 1) << 4) + i, a.T - 1);
-    const bool valid = live && ((tile << 4) + i) < a.T;
-    const int nch = (a.C + CWK - 1) / CWK;
-    const int ch0 = blockIdx.x * chunks_per_block, ch1 = min(nch, ch0 + chunks_per_block);
-    if (ch0 >= ch1) return;
-    const bf16x8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
-
-    // the dx tiles: two in flight (the next chunk's is requested before the current one is computed)
-    unsigned char* orow0 = a.out + ((size_t)t * a.C + 8 * g) * 2;
-    bf16x8 oA[NQ], oB[NQ];
-    auto issue_o = [&](bf16x8 (&o)[NQ], int ch_) {
-        const int cb = min(ch_, ch1 - 1) * CWK;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) o[q] = *(const bf16x8*)(orow0 + (size_t)min(cb + 32 * q, a.C - 32) * 2);
-    };
-    issue_o(oA, ch0);
-
-    // my token's pack rows of the G projections: B fragments [hi | lo] x KH, resident
-    bf16x8 bh[G][KH], bl[G][KH];
-#pragma unroll
-    for (int gi = 0; gi < G; ++gi) {
-        const unsigned char* prp = (const unsigned char*)ab.z[gi].pack + (size_t)t * (2 * RP * 2);
-#pragma unroll
-        for (int kh = 0; kh < KH; ++kh) {
-            if (RP == 16) { bh[gi][kh] = *(const bf16x8*)(prp + 16 * g); bl[gi][kh] = bh[gi][kh]; }    // K = 32 is [hi(16) | lo(16)]: one MFMA
-            else {
-                bh[gi][kh] = *(const bf16x8*)(prp + (32 * kh + 8 * g) * 2);
-                bl[gi][kh] = *(const bf16x8*)(prp + (RP + 32 * kh + 8 * g) * 2);
-            }
-        }
-    }
-    const int mrow = live ? (int)a.tok_mod[(tile << 4) + i] : MOKA_MOD_NONE;     // padded past T with MOKA_MOD_NONE
-    unsigned pm = 0;
-#pragma unroll
-    for (int m = 0; m < MOKA_MAX_MOD; ++m) if (m < a.M && __any(mrow == m)) pm |= 1u << m;
-    if (lane == 0) s_wpm[wave] = pm;
-    __syncthreads();
-    unsigned pmB = 0;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) pmB |= s_wpm[w];
-    if (pmB == 0) return;                                                    // a run of padding only (block uniform)
-
-    // walk steps: (chunk, modality of the run) pairs; the fragments of the next step are requested while the current one is multiplied
-    bf16x8 wp[PER];
-    auto wload = [&](int ch, int m) {
-        const int cb = ch * CWK;
-        const unsigned char* wm[G];
-#pragma unroll
-        for (int gi = 0; gi < G; ++gi) wm[gi] = ab.z[gi].W[0] + (size_t)m * a.C * RP * 2;      // (the shadows of the modalities follow each other)
-#pragma unroll
-        for (int u = 0; u < PER; ++u) {
-            const int e = tid + 512 * (u % PG);                              // (q, p, kh, lane) of projection u / PG: NF x 64 fragments each
-            const int ln = e & 63, kh = (e >> 6) % KH, p = ((e >> 6) / KH) & 1, q = (e >> 6) / (2 * KH);
-            const int c = min(cb + 32 * q + 8 * ((ln & 15) >> 2) + 4 * p + (ln & 3), a.C - 1);   // columns >= C are never stored
-            const int k0 = (RP == 16) ? 8 * ((ln >> 4) & 1) : 32 * kh + 8 * (ln >> 4);
-            wp[u] = *(const bf16x8*)(wm[u / PG] + ((size_t)c * RP + k0) * 2);
-        }
-    };
-    auto step = [&](bf16x8 (&o)[NQ], bf16x8 (&onext)[NQ], int ch) {
-        const int cb = ch * CWK;
-        issue_o(onext, ch + 1);
-        float sum[NQ][8];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) sum[q][e] = 0.f;
-        unsigned rest = pmB;
-        while (rest) {                                                       // block uniform
-            const int m = __builtin_ctz(rest);
-            rest &= rest - 1;
-            __syncthreads();                                                 // the previous step's fragments are no longer read
-#pragma unroll
-            for (int u = 0; u < PER; ++u) wl[tid + 512 * u] = wp[u];
-            __syncthreads();
-            if (rest) wload(ch, __builtin_ctz(rest));
-            else if (ch + 1 < ch1) wload(ch + 1, __builtin_ctz(pmB));
-            if (!(pm & (1u << m))) continue;                                 // none of my tokens has this modality (wave uniform)
-            const bool mine = mrow == m;
-            // (the keep masks do not depend on the modality: left alone the compiler computes the G x NQ masks of a chunk in front of
-            //  this loop and keeps 48 registers for them -- 62 spills at G = 3; opaque, they are made where they are used)
-            unsigned trow = (unsigned)t;
-            asm volatile("" : "+v"(trow));
-#pragma unroll
-            for (int gi = 0; gi < G; ++gi) {
-                const ExpandArgs& ag = ab.z[gi];
-#pragma unroll
-                for (int q = 0; q < NQ; ++q) {
-                    // (one 32-column block at a time: 4 fragments from LDS, 8 MFMAs, its epilogue -- the fence keeps the compiler from
-                    //  fetching the fragments of all blocks first, which costs 77 spilled registers at G = 3)
-                    f32x4 d[2];
-#pragma unroll
-                    for (int p = 0; p < 2; ++p) {
-                        d[p] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                        for (int kh = 0; kh < KH; ++kh) {
-                            const bf16x8 wf = wl[(((size_t)gi * NQ + q) * 2 + p) * KH * 64 + kh * 64 + lane];
-                            d[p] = MFMA16(wf, bh[gi][kh], d[p]);
-                            if (RP != 16) d[p] = MFMA16(wf, bl[gi][kh], d[p]);
-                        }
-                    }
-                    float v[8];
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = mine ? d[e >> 2][e & 3] : 0.f;
-                    float dsc = 1.f;
-                    if (ag.drop.thr) {
-                        const KeepMask keep = drop_keep8(ag.drop, ep, trow * (unsigned)(a.C >> 3) + (unsigned)((cb + 32 * q) >> 3) + (unsigned)g);
-                        dsc = ag.drop.inv_keep;
-#pragma unroll
-                        for (int w2 = 0; w2 < 4; ++w2) {
-                            const int mlo = __builtin_amdgcn_sbfe((int)keep.w[w2], 0, 16), mhi = (int)keep.w[w2] >> 16;
-                            v[2 * w2] = __int_as_float(__float_as_int(v[2 * w2]) & mlo);
-                            v[2 * w2 + 1] = __int_as_float(__float_as_int(v[2 * w2 + 1]) & mhi);
-                        }
-                    }
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) sum[q][e] = fmaf(v[e], dsc, sum[q][e]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        }
-        if (pm) {
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                if (cb + 32 * q >= a.C) continue;                            // C % 32 == 0
-                union { bf16x8 b; unsigned u[4]; } ou, res;
-                ou.b = o[q];
-#pragma unroll
-                for (int w2 = 0; w2 < 4; ++w2)
-                    res.u[w2] = f2bf_pk(__uint_as_float(ou.u[w2] << 16) + sum[q][2 * w2], __uint_as_float(ou.u[w2] & 0xffff0000u) + sum[q][2 * w2 + 1]);
-                if (valid) *(bf16x8*)(orow0 + (size_t)(cb + 32 * q) * 2) = res.b;
-            }
-        }
-    };
-    wload(ch0, __builtin_ctz(pmB));
-    for (int ch = ch0; ch < ch1; ch += 2) {
-        step(oA, oB, ch);
-        if (ch + 1 < ch1) step(oB, oA, ch + 1);
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// E (rank pad 64): y += hp . Bw^T in the token-owning form of moka_dxg_kernel: a workgroup keeps 128 tokens (wave w the 16-token tile w,
+// E (rank pad 64): y += hp . Bw^T in the token-owning form: a workgroup keeps 128 tokens (wave w the 16-token tile w,
 // its (hi, lo) pack row resident: 16 registers) and walks its column range in chunks of 128; the chunk's 16 KB of Bw are staged in LDS
 // for the eight waves, requested from L2 one chunk ahead.  ~100 registers instead of the 260 of the column-owning kernel (one wave per
 // SIMD, every wave reading its 256-byte pack rows and holding 64 registers of weights): four waves per SIMD.  blockIdx.z = problem.
@@ -612,7 +448,7 @@ __global__ void __launch_bounds__(512, 4) moka_yt_kernel(const ExpandBatch ab, i
 // (Until round 6 the kernel walked its columns once per modality of the run: the launches are one round of workgroups, so the few
 // two-walk workgroups set the launch time -- 13B widths, 2 x 4096 tokens: o 70.5 us with the bench layout against 47.4 us text only, down
 // 175.9 against 112.6.)
-// Replaces moka_expand_kernel<64, 4, false, 1, 2, true> (256 registers, one wave per SIMD: 13B widths, dx of o / down 2.7 TB/s).
+// Replaces the column-owning form, moka_expand_kernel<64, 4, false, 1, true> (256 registers, one wave per SIMD: 13B widths, dx of o / down 2.7 TB/s).
 // ------------------------------------------------------------------------------------------
 template <int RP>
 __global__ void __launch_bounds__(512, 4) moka_dxt_kernel(const ExpandBatch ab, int chunks_per_block) {
@@ -759,8 +595,13 @@ __global__ void __launch_bounds__(512, 4) moka_dxt_kernel(const ExpandBatch ab, 
 }
 
 // ------------------------------------------------------------------------------------------
-// E (rank pads 32 / 64, G > 1): moka_dxg_kernel in the lean form of moka_dxt_kernel -- ONE walk over the workgroup's columns, the G products of a
-// 32-column block formed back to back into one fp32 sum of 8 registers.  The weights of the token run's lowest modality are staged a chunk ahead;
+// E (rank pads 32 / 64, G > 1): dx += sum_g mask_g o (dh_g . A_g,m(t))  in ONE read-modify-write pass over dx: q/k/v (gate/up) cost one pass
+// instead of three (two).  The per-wave-resident weights of moka_expand_kernel do not fit three projections at these ranks (250 registers, one
+// wave per SIMD: it lost), so the roles are turned round as in moka_dxt_kernel: a workgroup (8 waves) keeps 128 TOKENS -- wave w the 16-token tile
+// w, its G x (hi, lo) pack rows resident as MFMA B fragments -- and walks the columns in chunks of 128; the chunk's weights of all G projections
+// are staged in LDS for the eight waves, requested from L2 one step ahead into registers (the moka_xwm_kernel scheme).  ONE walk over the
+// workgroup's columns, the G products of a 32-column block formed back to back into one fp32 sum of 8 registers; each projection's product passes
+// its own dropout mask before it joins the sum, and the dx tile is written once per chunk.  The weights of the token run's lowest modality are staged a chunk ahead;
 // those of its other modalities (span boundaries only) go into further slots of G x 8 / 16 KB behind the chunk's barrier, and a wave takes the slot of
 // its 16 tokens' modality (a tile across a span boundary: once per modality it holds, selected per lane).
 // (Until round 6: one walk per modality of the run -- 7B widths, r = 32, 4096 tokens per launch: q+k+v 36.5 us with the bench layout against 28.4 us
@@ -865,7 +706,7 @@ __global__ void __launch_bounds__(512, RP == 16 ? 4 : 3) moka_dxgt_kernel(const 
         __syncthreads();
         if (ch + 1 < ch1) wload(ch + 1);
         if (!pm) return;                                                     // a tile of padding
-        asm volatile("" : "+v"(trow));                                       // (the masks are made where they are used: see moka_dxg_kernel)
+        asm volatile("" : "+v"(trow));                                       // (opaque to the compiler, so the keep masks -- which do not depend on the modality -- are made where they are used, not G x NQ of them ahead of the loop)
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
             float sum[8];
@@ -1015,7 +856,7 @@ __global__ void __launch_bounds__(512, RP == 64 ? 2 : YX_MINW) moka_yx_kernel(co
         f32x4 accR[IPT];
 #pragma unroll
         for (int u = 0; u < IPT; ++u) accR[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        const int ks_eff = (fb.dbg & 2) ? 1 : fb.ks;
+        const int ks_eff = (fb.dbg & 2) ? 1 : fb.ks;             // (fb.dbg is always 0: see YxBatch)
         for (int s0 = 0; s0 < ks_eff; s0 += SB) {
             f32x4 xr[IPT][SB];
 #pragma unroll
@@ -1246,7 +1087,7 @@ __global__ void __launch_bounds__(512, RP == 64 ? 2 : YX_MINW) moka_yx_kernel(co
 // ------------------------------------------------------------------------------------------
 // launch helpers (host)
 // ------------------------------------------------------------------------------------------
-template <int RP, int NQ, bool W_CK, int G, int DEPTH, bool RUNS = false>
+template <int RP, int NQ, bool W_CK, int G, bool RUNS = false>
 static void launch_expand_t(const ExpandBatch& ab, int nz, hipStream_t st) {
     constexpr int CW = 4 * NQ * 32;
     int Cmax = 0;
@@ -1256,7 +1097,7 @@ static void launch_expand_t(const ExpandBatch& ab, int nz, hipStream_t st) {
     // (wide launches: 8 workgroups per CU when the launch has the chip to itself; beside another chain (moka_opts.company > 1) THREE -- fewer, longer workgroups while the
     //  other chain's launch fills the rest: the dx pass of the 11008-wide input, two chains of 4096 tokens: 29.57 -> 29.36 / 29.47, 30.45 -> 30.25, 30.62 -> 30.31 ms per step on
     //  two boxes, 13B widths 47.85 -> 47.40, 47.28 -> 46.98; one chain: 31.86 -> 31.96 (stays at 8); the narrow launches stay at 2: 3 loses 0.1-0.2 ms)
-    const int bpc = g_tune_expand_bpc > 0 ? g_tune_expand_bpc : ((Cmax > 8192 || (W_CK && nz > 1)) ? (t_company > 1 ? 3 : 8) : 2);
+    const int bpc = (Cmax > 8192 || (W_CK && nz > 1)) ? (t_company > 1 ? 3 : 8) : 2;
     // the x dimension of the grid enumerates the column blocks of all batched problems (xend): grouped-query k / v beside q are
     // 16 + 2 + 2 column blocks, not 3 x 16
     ExpandBatch sb = ab;
@@ -1271,9 +1112,9 @@ static void launch_expand_t(const ExpandBatch& ab, int nz, hipStream_t st) {
     if (gy < 1) gy = 1;
     if (G > 1 || uniform) {
         for (int z = 0; z < MOKA_MAX_GROUP; ++z) sb.xend[z] = 0;      // a grid row per problem
-        hipLaunchKernelGGL((moka_expand_kernel<RP, NQ, W_CK, G, DEPTH, RUNS>), dim3(nc, gy, G == 1 ? nz : 1), dim3(256), 0, st, sb);
+        hipLaunchKernelGGL((moka_expand_kernel<RP, NQ, W_CK, G, RUNS>), dim3(nc, gy, G == 1 ? nz : 1), dim3(256), 0, st, sb);
     } else {
-        hipLaunchKernelGGL((moka_expand_kernel<RP, NQ, W_CK, G, DEPTH, RUNS>), dim3(active, gy, 1), dim3(256), 0, st, sb);
+        hipLaunchKernelGGL((moka_expand_kernel<RP, NQ, W_CK, G, RUNS>), dim3(active, gy, 1), dim3(256), 0, st, sb);
     }
 }
 
@@ -1284,7 +1125,7 @@ static int launch_yt(const ExpandBatch& ab, int nz, hipStream_t st) {
     const int T = ab.z[0].T, nch = (Cmax + 127) / 128, ntb = (T + 127) / 128;
     // workgroups per CU (13B widths, r = 64, up_fwd per pass with 2 / 3 / 4 / 6 / 8: 17.0 / 16.4 / 17.4 / 16.8 / 17.0 ms; single launches are best at 2, batches at 3)
     // (r = 16, 7B widths: gate+up 150.3 / 146.8 / 146.0 / 154.2 us with 3 / 2 / 4 / 6, q+k+v 80.3 / 91.7 / 89.5 / 77.7)
-    const int bpc = g_tune_expand_bpc > 0 ? g_tune_expand_bpc : (RP == 64 ? (nz > 1 ? 3 : 2) : (Cmax > 8192 ? 4 : 6));
+    const int bpc = RP == 64 ? (nz > 1 ? 3 : 2) : (Cmax > 8192 ? 4 : 6);
     int want = (bpc * num_cu() + ntb * nz - 1) / (ntb * nz);
     want = want < 1 ? 1 : (want > nch ? nch : want);
     const int cpb = (nch + want - 1) / want;
@@ -1303,16 +1144,13 @@ static int launch_yx(const YxBatch& fb, int nz, hipStream_t st) {
     // column ranges per token block: every range repeats the prologue (ks x 64 B per token from L2 + the sample's key rows), so few --
     // four (7B widths, 8192 tokens, cpb = 2 / 4 / 8 / 16 at 4096 columns: o 43.0 / 39.2 / 35.8 / 57.4 us, q+k+v 101.9 / 92.7 / 85.0 / 105.5;
     // gate+up 22 / 16 / 8 chunks per range: 149.6 / 169.2 / 161.1), more only where fewer tokens would leave CUs without a workgroup
-    // ("yx_bpc": workgroups per CU instead; "yx_cpb": chunks per range)
     // rank pad 32: three workgroups per CU instead (r = 32, two chains of 4096 tokens, yx_bpc 0 / 2 / 3 / 4 / 6: 37.5 / 37.1 / 37.0 / 38.2 / 38.8 ms per step;
     // r = 16 the same settings: 30.3 / 31.0 / 31.3 / 31.5 / 31.9 -- four ranges stay there)
-    const int bpc = g_tune_yx_bpc > 0 ? g_tune_yx_bpc : (RP == 32 ? 3 : 0);
-    int want = bpc > 0 ? (bpc * num_cu() + ntb * nz - 1) / (ntb * nz) : 4;
-    // ("yx_fill" 1: never more than four ranges; 2: two ranges for single projections)
-    if (g_tune_yx_fill == 2 && nz == 1) want = 2;
-    if (bpc <= 0 && g_tune_yx_fill == 0 && (long)want * ntb * nz < (long)num_cu()) want = (num_cu() + ntb * nz - 1) / (ntb * nz);
+    int want = 4;
+    if (RP == 32) want = (3 * num_cu() + ntb * nz - 1) / (ntb * nz);
+    else if ((long)want * ntb * nz < (long)num_cu()) want = (num_cu() + ntb * nz - 1) / (ntb * nz);
     want = want < 1 ? 1 : (want > nch ? nch : want);
-    const int cpb = g_tune_yx_cpb > 0 ? g_tune_yx_cpb : (nch + want - 1) / want;
+    const int cpb = (nch + want - 1) / want;
     constexpr size_t lds_w = (size_t)4 * 2 * ((RP + 31) / 32) * 1024, lds_p = (size_t)(8 * 2 * 16 + 64) * (RP + 1) * 4;
     constexpr size_t lds = lds_w > lds_p ? lds_w : lds_p;
     ensure_lds((const void*)moka_yx_kernel<RP>, lds);
@@ -1320,87 +1158,57 @@ static int launch_yx(const YxBatch& fb, int nz, hipStream_t st) {
     return check_launch("moka_yx_kernel");
 }
 
-// W_CK: nz batched problems (G = 1 inside the kernel).  !W_CK: nz = number of projections sharing dx.
+// the token-owning dx forms (moka_dxt_kernel, moka_dxgt_kernel): column ranges so that every CU gets `bpc` workgroups of 128 tokens
+template <typename K>
+static void launch_dx_tok(K kernel, size_t lds, int bpc, const ExpandBatch& ab, hipStream_t st) {
+    const int T = ab.z[0].T, C = ab.z[0].C;
+    const int nch = (C + 127) / 128, ntb = (T + 127) / 128;
+    int want = (bpc * num_cu() + ntb - 1) / ntb;
+    want = want < 1 ? 1 : (want > nch ? nch : want);
+    const int cpb = (nch + want - 1) / want;
+    ensure_lds((const void*)kernel, lds);
+    hipLaunchKernelGGL(kernel, dim3((nch + cpb - 1) / cpb, ntb), dim3(512), lds, st, ab, cpb);
+}
+
+// W_CK (y += hp.Bw^T): nz batched problems (G = 1 inside the kernel).  !W_CK (dx): nz = number of projections sharing dx.
 template <bool W_CK>
 static int launch_expand(const ExpandBatch& ab, int nz, int RP, hipStream_t st) {
-    // two tiles in flight per wave everywhere (measured: 3-4 deep rings gain nothing once loads and stores are unconditional)
-    if (W_CK || nz == 1) {
-        // RP == 16: the per-tile form (text set resident, the others fetched for the tiles that need them); contiguous runs with one
-        // resident set lose there (dx pass 11.1 -> 11.8 ms), win at rank pad 32 (16.2 -> 15.9) and 64 (37.4 -> 30.7, with 128 columns per wave)
+    if constexpr (W_CK) {
+        if (RP == 64) return launch_yt<64>(ab, nz, st);  // the token-owning y kernel (measured and lost: the column-owning forms)
         // r <= 32: the token-owning form for BATCHED launches of equal, moderate width (7B widths, r = 16: gate+up 155.8 -> 146.0 us, q+k+v 84.1 -> 77.7,
         // step 34.14 -> 33.93 ms on one box, twice; 70B gate+up, 2 x 28672: up_fwd 48.7 -> 45.2 ms per pass, step 161.9 -> 160.7 ms); single
         // projections stay (32.0 -> 32.2-33.6 us), and so do batches of different width (70B q / k / v = 8192 / 1024 / 1024: with them the
-        // step went 165.8 -> 167.6 ms).  "expand_nq" 5 / 6: always / never.
-        if (RP <= 32 && W_CK && g_tune_expand_nq != 6) {
-            bool uniform = true;
-            size_t cols = 0;
-            for (int z = 0; z < nz; ++z) { uniform = uniform && ab.z[z].C == ab.z[0].C; cols += (size_t)ab.z[z].C; }
-            if (g_tune_expand_nq == 5 || (nz > 1 && uniform && cols <= 65536)) return RP == 16 ? launch_yt<16>(ab, nz, st) : launch_yt<32>(ab, nz, st);
-        }
-        if (RP == 16) { if (g_tune_expand_depth == 3) launch_expand_t<16, 4, W_CK, 1, 3>(ab, nz, st); else launch_expand_t<16, 4, W_CK, 1, 2>(ab, nz, st); }
-        // wider ranks: the y kernel keeps 128 columns per wave (r = 64: 48 -> 34 us at 4096), the dx kernel 64
-        else if (RP == 32) {
-            if (W_CK) { if (g_tune_expand_nq != 2) launch_expand_t<32, 4, true, 1, 2>(ab, nz, st); else launch_expand_t<32, 2, true, 1, 2>(ab, nz, st); }
-            else if (g_tune_expand_nq == 3) launch_expand_t<32, 2, false, 1, 2>(ab, nz, st);        // the per-tile form (A/B)
-            else launch_expand_t<32, 4, false, 1, 2, true>(ab, nz, st);
-        }
-        else if (W_CK && g_tune_expand_nq == 0) {        // rank pad 64: the token-owning y kernel ("expand_nq" 2 / 4: the column-owning forms)
-            return launch_yt<64>(ab, nz, st);
-        }
-        else if (W_CK) { if (g_tune_expand_nq == 2) launch_expand_t<64, 2, true, 1, 2>(ab, nz, st); else launch_expand_t<64, 4, true, 1, 2>(ab, nz, st); }
-        else if (g_tune_expand_nq == 3) launch_expand_t<64, 2, false, 1, 2>(ab, nz, st);            // the per-tile form (A/B)
-        // (the token-owning form of the groups, moka_dxg_kernel<1>, loses for a single projection: dx + dA of o / down 97 / 227 -> 109 / 253 us;
-        //  the lean one, moka_dxt_kernel -- moka_yt_kernel's walk once per modality of the run -- wins; "expand_nq" 4: the column-owning form)
-        else if (g_tune_expand_nq == 4) launch_expand_t<64, 4, false, 1, 2, true>(ab, nz, st);
+        // step went 165.8 -> 167.6 ms)
+        bool uniform = true;
+        size_t cols = 0;
+        for (int z = 0; z < nz; ++z) { uniform = uniform && ab.z[z].C == ab.z[0].C; cols += (size_t)ab.z[z].C; }
+        if (nz > 1 && uniform && cols <= 65536) return RP == 16 ? launch_yt<16>(ab, nz, st) : launch_yt<32>(ab, nz, st);
+        // the column-owning y kernel keeps 128 columns per wave
+        if (RP == 16) launch_expand_t<16, 4, true, 1>(ab, nz, st);
+        else launch_expand_t<32, 4, true, 1>(ab, nz, st);
+    } else if (nz == 1) {
+        // RP == 16: the per-tile form (text set resident, the others fetched for the tiles that need them); contiguous runs with one
+        // resident set lose there (dx pass 11.1 -> 11.8 ms), win at rank pad 32 (16.2 -> 15.9)
+        if (RP == 16) launch_expand_t<16, 4, false, 1>(ab, nz, st);
+        else if (RP == 32) launch_expand_t<32, 4, false, 1, true>(ab, nz, st);
         else {
-            const int T = ab.z[0].T, C = ab.z[0].C;
-            const int nch = (C + 127) / 128, ntb = (T + 127) / 128;
-            int want = ((g_tune_expand_bpc > 0 ? g_tune_expand_bpc : 2) * num_cu() + ntb - 1) / ntb;
-            want = want < 1 ? 1 : (want > nch ? nch : want);
-            const int cpb = (nch + want - 1) / want;
-            constexpr size_t lds = (size_t)MOKA_MAX_MOD * 4 * 2 * 2 * 1024;        // a 16 KB slot per modality of the token run
-            ensure_lds((const void*)moka_dxt_kernel<64>, lds);
-            hipLaunchKernelGGL((moka_dxt_kernel<64>), dim3((nch + cpb - 1) / cpb, ntb), dim3(512), lds, st, ab, cpb);
+            // rank pad 64: the lean token-owning form -- moka_yt_kernel's walk once per modality of the run; two workgroups per CU
+            // (measured and lost: the column-owning forms, and the first token-owning form of the groups for a single projection:
+            //  dx + dA of o / down 97 / 227 -> 109 / 253 us)
+            launch_dx_tok(moka_dxt_kernel<64>, (size_t)MOKA_MAX_MOD * 4 * 2 * 2 * 1024, 2, ab, st);       // a 16 KB slot per modality of the token run
             return check_launch("moka_dxt_kernel");
         }
-    } else if (RP == 64 || RP == 32) {                   // projections sharing dx at rank pads 32 / 64: the token-owning form (moka_dxg_kernel)
-        const int T = ab.z[0].T, C = ab.z[0].C;
-        const int nch = (C + 127) / 128, ntb = (T + 127) / 128;
+    } else if (RP >= 32) {                               // projections sharing dx at rank pads 32 / 64: the token-owning form
         // column ranges: three workgroups per CU, one resident (13B widths, dx + dA per pass with 1 / 2 / 3 / 4 / 6: 29.4 / 28.3 / 27.7 / 28.1 / 28.4 ms; per-projection passes: 30.7)
-        int want = ((g_tune_dx_group >= 2 ? g_tune_dx_group - 1 : 3) * num_cu() + ntb - 1) / ntb;
-        want = want < 1 ? 1 : (want > nch ? nch : want);
-        const int cpb = (nch + want - 1) / want;
-        const dim3 grid((nch + cpb - 1) / cpb, ntb);
-        auto go = [&](auto kernel, size_t lds) {
-            ensure_lds((const void*)kernel, lds);
-            hipLaunchKernelGGL(kernel, grid, dim3(512), lds, st, ab, cpb);
-        };
-        if (g_tune_g32_dx == 3) {                        // ("g32_dx" 3: the first form, moka_dxg_kernel -- A/B)
-            if (RP == 64) { if (nz == 2) go(moka_dxg_kernel<64, 2>, (size_t)2 * 16 * 1024); else go(moka_dxg_kernel<64, 3>, (size_t)3 * 16 * 1024); }
-            else          { if (nz == 2) go(moka_dxg_kernel<32, 2>, (size_t)2 * 8 * 1024); else go(moka_dxg_kernel<32, 3>, (size_t)3 * 8 * 1024); }
-            return check_launch("moka_dxg_kernel");
-        }
-        if (RP == 64) { if (nz == 2) go(moka_dxgt_kernel<64, 2>, (size_t)MOKA_MAX_MOD * 2 * 16 * 1024); else go(moka_dxgt_kernel<64, 3>, (size_t)MOKA_MAX_MOD * 3 * 16 * 1024); }
-        else          { if (nz == 2) go(moka_dxgt_kernel<32, 2>, (size_t)MOKA_MAX_MOD * 2 * 8 * 1024); else go(moka_dxgt_kernel<32, 3>, (size_t)MOKA_MAX_MOD * 3 * 8 * 1024); }
+        if (RP == 64) { if (nz == 2) launch_dx_tok(moka_dxgt_kernel<64, 2>, (size_t)MOKA_MAX_MOD * 2 * 16 * 1024, 3, ab, st); else launch_dx_tok(moka_dxgt_kernel<64, 3>, (size_t)MOKA_MAX_MOD * 3 * 16 * 1024, 3, ab, st); }
+        else          { if (nz == 2) launch_dx_tok(moka_dxgt_kernel<32, 2>, (size_t)MOKA_MAX_MOD * 2 * 8 * 1024, 3, ab, st); else launch_dx_tok(moka_dxgt_kernel<32, 3>, (size_t)MOKA_MAX_MOD * 3 * 8 * 1024, 3, ab, st); }
         return check_launch("moka_dxgt_kernel");
-    } else {                                             // can_group(): RP == 16 -- projections sharing dx: ONE read-modify-write pass
+    } else {                                             // RP == 16 -- projections sharing dx: ONE read-modify-write pass
         // (the same kernel at rank pad 64: the G = 3 instance needs 250 VGPRs, one wave per SIMD, and lost: 45.8 -> 47.2 ms per backward pass;
-        //  the token-owning form of rank pad 64, moka_dxg_kernel<16, G>, loses here: q+k+v dx + dA 88.9 -> 106.4 us, gate+up 70.3 -> 84.9)
-        // ("g32_dx" 4: the token-owning lean form, moka_dxgt_kernel<16, G>, at r <= 16 too: dx + dA of q+k+v 88.7 -> 93.0 us, gate+up 70.8 -> 75.8,
+        //  the token-owning forms of the wider ranks lose here: q+k+v dx + dA 88.7 -> 93.0 us, gate+up 70.8 -> 75.8,
         //  step 32.6 -> 33.0-33.2 ms -- the column-owning form with resident weights stays)
-        if (g_tune_g32_dx == 4) {
-            const int T = ab.z[0].T, C = ab.z[0].C;
-            const int nch = (C + 127) / 128, ntb = (T + 127) / 128;
-            int want = ((g_tune_dx_group >= 2 ? g_tune_dx_group - 1 : 4) * num_cu() + ntb - 1) / ntb;
-            want = want < 1 ? 1 : (want > nch ? nch : want);
-            const int cpb = (nch + want - 1) / want;
-            const dim3 grid((nch + cpb - 1) / cpb, ntb);
-            if (nz == 2) { ensure_lds((const void*)moka_dxgt_kernel<16, 2>, (size_t)MOKA_MAX_MOD * 2 * 8 * 1024); hipLaunchKernelGGL((moka_dxgt_kernel<16, 2>), grid, dim3(512), (size_t)MOKA_MAX_MOD * 2 * 8 * 1024, st, ab, cpb); }
-            else { ensure_lds((const void*)moka_dxgt_kernel<16, 3>, (size_t)MOKA_MAX_MOD * 3 * 8 * 1024); hipLaunchKernelGGL((moka_dxgt_kernel<16, 3>), grid, dim3(512), (size_t)MOKA_MAX_MOD * 3 * 8 * 1024, st, ab, cpb); }
-            return check_launch("moka_dxgt_kernel");
-        }
-        if (nz == 2) launch_expand_t<16, 2, false, 2, 2>(ab, 1, st);
-        else launch_expand_t<16, 2, false, 3, 2>(ab, 1, st);
+        if (nz == 2) launch_expand_t<16, 2, false, 2>(ab, 1, st);
+        else launch_expand_t<16, 2, false, 3>(ab, 1, st);
     }
     return check_launch("moka_expand_kernel");
 }

@@ -18,12 +18,11 @@
 //     in the wgrad kernel, reduced over the block at the end.
 // Replaces moka_reduce_kernel + moka_wgrad_kernel<OUT_CK> on gy, which each read gy once (measured: 36 us
 // for a 67 MB gy where one pass costs ~20 us).
-template <int RP, bool WITH_DB, int NG, bool DET, int KK = 2>
+template <bool WITH_DB, int NG, bool DET>
 __global__ void __launch_bounds__(512) moka_gy_kernel(const GyBatch ab) {
-    static_assert(KK == 2 || (KK == 4 && !WITH_DB), "KK = K steps (32 columns) per wave: 128 columns per wave only for the g-only form");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int NT = RP / 16;
-    constexpr int NW = 8, PH = (RP == 64) ? 1 : 2, CT = 4;   // NG = 32-token groups per block; PH: LDS budget (RP = 64: 64 KB of slots per phase)
+    constexpr int RP = 16, KK = 2;                       // rank pad; K steps (32 columns) per wave
+    constexpr int NW = 8, PH = 2, CT = 4;                // NG = 32-token groups per block; PH = groups per reduction phase
     constexpr int PITCH = 64 * 2 + 32, REGION = 32 * PITCH;
     constexpr int RSLOT = 32 * RP;                       // floats per (wave, group) partial
     // the x dimension of the grid enumerates the column blocks of all batched problems (a grid row per problem left a narrow member
@@ -59,22 +58,20 @@ __global__ void __launch_bounds__(512) moka_gy_kernel(const GyBatch ab) {
     float* myr = rbuf + (size_t)wave * PH * RSLOT;
 
     // weight fragments of my 64 columns (two K steps), resident: lane (n = rank i, k chunk g)
-    bf16x8 bwt[KK][NT];
+    bf16x8 bwt[KK];
 #pragma unroll
-    for (int kk = 0; kk < KK; ++kk)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int c = c0 + 32 * kk + 8 * g;
-            bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (c < a.C) v = *(const bf16x8*)(a.BwT + ((size_t)(nt * 16 + i) * a.C + c) * 2);
-            bwt[kk][nt] = v;
-        }
+    for (int kk = 0; kk < KK; ++kk) {
+        const int c = c0 + 32 * kk + 8 * g;
+        bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (c < a.C) v = *(const bf16x8*)(a.BwT + ((size_t)i * a.C + c) * 2);
+        bwt[kk] = v;
+    }
 
     const int grp_last = ngroups - 1;
     // F[st][kk]: rows 16st + i of the group, columns c0 + 32kk + 8g .. +7   (unconditional, clamped)
     // (the prefetch behind the block's last group is clamped to that group: its lines were requested a moment ago, so the
     //  unconditional load costs an L2 hit -- not a second HBM read of the NEXT block's first group, which was 1/NG of the traffic)
-    auto issue = [&](bf16x8 (&F)[2][KK], bf16x8 (&bh)[NT], bf16x8 (&bl)[NT], int grp_) {
+    auto issue = [&](bf16x8 (&F)[2][KK], bf16x8& bh, bf16x8& bl, int grp_) {
         const int grp = min(min(grp_, grp0 + NG - 1), grp_last);
 #pragma unroll
         for (int st = 0; st < 2; ++st) {
@@ -86,40 +83,33 @@ __global__ void __launch_bounds__(512) moka_gy_kernel(const GyBatch ab) {
             }
         }
         if (WITH_DB) {
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                const unsigned short* ph = kmj_frag<RP>(a.pack, 0, nt, grp, a.Tp, lane);
-                bh[nt] = *(const bf16x8*)ph;
-                bl[nt] = *(const bf16x8*)(ph + (size_t)RP * a.Tp);
-            }
+            const unsigned short* ph = kmj_frag<RP>(a.pack, 0, 0, grp, a.Tp, lane);
+            bh = *(const bf16x8*)ph;
+            bl = *(const bf16x8*)(ph + (size_t)RP * a.Tp);
         }
     };
-    f32x4 accW[CT][NT];
+    f32x4 accW[CT];
 #pragma unroll
-    for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) accW[ct][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int ct = 0; ct < CT; ++ct) accW[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    auto compute = [&](bf16x8 (&F)[2][KK], bf16x8 (&bh)[NT], bf16x8 (&bl)[NT], int gi) {
+    auto compute = [&](bf16x8 (&F)[2][KK], const bf16x8& bh, const bf16x8& bl, int gi) {
         const int grp = grp0 + gi;
         const bool live = wactive && grp < ngroups;      // wave uniform
         // ---- g: [32 tokens x RP] partial over my columns -> my LDS slot of this phase
         float* slot = myr + (size_t)(gi % PH) * RSLOT;
 #pragma unroll
-        for (int st = 0; st < 2; ++st)
+        for (int st = 0; st < 2; ++st) {
+            f32x4 accR = {0.f, 0.f, 0.f, 0.f};
+            if (live) {
+                const bf16x8 z8r = {0, 0, 0, 0, 0, 0, 0, 0};
+                accR = MFMA16(F[st][0], bwt[0], accR);
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                f32x4 accR = {0.f, 0.f, 0.f, 0.f};
-                if (live) {
-                    const bf16x8 z8r = {0, 0, 0, 0, 0, 0, 0, 0};
-                    accR = MFMA16(F[st][0], bwt[0][nt], accR);
-#pragma unroll
-                    for (int kk = 1; kk < KK; ++kk) accR = MFMA16((c0 + 32 * kk < a.C) ? F[st][kk] : z8r, bwt[kk][nt], accR);   // branch-free, see moka_xa_kernel
-                }
-                MFMA_SETTLE(accR);
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg) slot[(16 * st + 4 * g + reg) * RP + nt * 16 + i] = accR[reg];
+                for (int kk = 1; kk < KK; ++kk) accR = MFMA16((c0 + 32 * kk < a.C) ? F[st][kk] : z8r, bwt[kk], accR);   // branch-free, see moka_xa_kernel
             }
+            MFMA_SETTLE(accR);
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) slot[(16 * st + 4 * g + reg) * RP + i] = accR[reg];
+        }
         // ---- dB: transposed tile through the wave-private LDS region
         if (WITH_DB && live) {
             const bf16x8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -134,11 +124,8 @@ __global__ void __launch_bounds__(512) moka_gy_kernel(const GyBatch ab) {
                 const bf16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_TR_PTR(base));
                 const bf16x4 a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_TR_PTR(base + 16 * PITCH));
                 const bf16x8 av = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    accW[ct][nt] = MFMA16(av, bh[nt], accW[ct][nt]);
-                    accW[ct][nt] = MFMA16(av, bl[nt], accW[ct][nt]);
-                }
+                accW[ct] = MFMA16(av, bh, accW[ct]);
+                accW[ct] = MFMA16(av, bl, accW[ct]);
             }
         }
     };
@@ -158,7 +145,7 @@ __global__ void __launch_bounds__(512) moka_gy_kernel(const GyBatch ab) {
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     };
 
-    bf16x8 FA[2][KK], FB[2][KK], bhA[NT], blA[NT], bhB[NT], blB[NT];
+    bf16x8 FA[2][KK], FB[2][KK], bhA, blA, bhB, blB;
     issue(FA, bhA, blA, grp0);
 #pragma unroll
     for (int gi = 0; gi < NG; gi += 2) {
@@ -166,37 +153,28 @@ __global__ void __launch_bounds__(512) moka_gy_kernel(const GyBatch ab) {
         compute(FA, bhA, blA, gi);
         if (gi == 0) TRACE(1);
         issue(FA, bhA, blA, grp0 + gi + 2);
-        if (PH == 1) reduce_phase(gi);
         compute(FB, bhB, blB, gi + 1);
         if (gi == 0) TRACE(2);
-        if (PH == 1) reduce_phase(gi + 1);
-        else reduce_phase(gi / 2);
+        reduce_phase(gi / 2);
         if (gi == 0) TRACE(3);
     }
     TRACE(6);
 
     if (WITH_DB) {
         // dB leaves as [column][rank] rows: wave w's accumulators hold columns cb0 + 64w .. of it, the destination rows of the waves
-        // are disjoint, so there is no cross-wave sum -- only a wave-private transposition through LDS (own tile region for RP = 16,
-        // own slot area -- free after the last reduce_phase barrier -- for the wider ranks, CTB column tiles at a time)
-        constexpr int CTB = (RP == 64) ? 2 : CT;
-        float* mine = (RP == 16) ? (float*)my : myr;
+        // are disjoint, so there is no cross-wave sum -- only a wave-private transposition through LDS (the wave's own tile region)
+        float* mine = (float*)my;
 #pragma unroll
-        for (int cb = 0; cb < CT; cb += CTB) {
+        for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
-            for (int ct = 0; ct < CTB; ++ct)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                    for (int reg = 0; reg < 4; ++reg) mine[(ct * 16 + 4 * g + reg) * RP + nt * 16 + i] = accW[cb + ct][nt][reg];
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            for (int e = lane; e < CTB * 16 * RP; e += 64) {
-                const int cl = e / RP, k = e % RP;
-                const int c = c0 + cb * 16 + cl;
-                if (c < a.C && k < a.r) {
-                    if (DET) a.det[((size_t)blockIdx.y * a.det_planes + zi) * a.det_stride + (size_t)c * a.r + k] = mine[cl * RP + k];
-                    else atomicAdd(a.dB + (size_t)c * a.r + k, mine[cl * RP + k]);
-                }
+            for (int reg = 0; reg < 4; ++reg) mine[(ct * 16 + 4 * g + reg) * RP + i] = accW[ct][reg];
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        for (int e = lane; e < CT * 16 * RP; e += 64) {
+            const int cl = e / RP, k = e % RP;
+            const int c = c0 + cl;
+            if (c < a.C && k < a.r) {
+                if (DET) a.det[((size_t)blockIdx.y * a.det_planes + zi) * a.det_stride + (size_t)c * a.r + k] = mine[cl * RP + k];
+                else atomicAdd(a.dB + (size_t)c * a.r + k, mine[cl * RP + k]);
             }
         }
     }
@@ -396,11 +374,11 @@ __global__ void __launch_bounds__(512) moka_gs_kernel(const GyBatch ab, int NG) 
 // stream is x alone: no weight traffic, and a group that straddles a span boundary costs one extra MFMA chain
 // (rows of the other modality zeroed in the x operand) instead of extra loads.  The [32 x 16] partial of a group
 // goes to a wave-private LDS slot; every PH groups the eight waves' slots are summed into one split-K slice.
-template <int RP, int G, int NG>
+template <int G, int NG>
 __global__ void __launch_bounds__(512) moka_xa_kernel(const XaArgs a) {
     const uint2 ep = drop_epoch(a.drop[0]);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int NT = RP / 16, NW = 8, PH = 2;
+    constexpr int RP = 16, NT = RP / 16, NW = 8, PH = 2;      // (NT = 1 rank tile: the accumulator stays an array, as in the wider kernels)
     constexpr int RSLOT = 32 * RP;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = lane & 15, g = lane >> 4;
@@ -414,21 +392,19 @@ __global__ void __launch_bounds__(512) moka_xa_kernel(const XaArgs a) {
     float* rbuf = (float*)smem;                              // [NW][PH][G][32][RP]
     float* myr = rbuf + (size_t)wave * PH * G * RSLOT;
 
-    bf16x8 wfr[G][MOKA_MAX_MOD][2][NT];
+    bf16x8 wfr[G][MOKA_MAX_MOD][2];
 #pragma unroll
     for (int gi = 0; gi < G; ++gi)
 #pragma unroll
         for (int m = 0; m < MOKA_MAX_MOD; ++m)
 #pragma unroll
-            for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const int c = c0 + 32 * kk + 8 * g;
-                    bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-                    // rank rows >= r do not exist: clamp the row, the result column is zeroed when the slice is written
-                    if (m < a.M && c < a.C) v = *(const bf16x8*)(a.A[gi][m] + ((size_t)min(nt * 16 + i, a.r - 1) * a.C + c) * 2);
-                    wfr[gi][m][kk][nt] = v;
-                }
+            for (int kk = 0; kk < 2; ++kk) {
+                const int c = c0 + 32 * kk + 8 * g;
+                bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+                // rank rows >= r do not exist: clamp the row, the result column is zeroed when the slice is written
+                if (m < a.M && c < a.C) v = *(const bf16x8*)(a.A[gi][m] + ((size_t)min(i, a.r - 1) * a.C + c) * 2);
+                wfr[gi][m][kk] = v;
+            }
 
     const int grp_last = ngroups - 1;
     auto issue = [&](bf16x8 (&F)[2][2], int (&mr)[2], int grp_) {
@@ -481,8 +457,8 @@ __global__ void __launch_bounds__(512) moka_xa_kernel(const XaArgs a) {
                         const bf16x8 x1 = (other || c0 + 32 >= a.C) ? z8 : xg[1];
 #pragma unroll
                         for (int nt = 0; nt < NT; ++nt) {
-                            acc[nt] = MFMA16(x0, wfr[gi][m][0][nt], acc[nt]);
-                            acc[nt] = MFMA16(x1, wfr[gi][m][1][nt], acc[nt]);
+                            acc[nt] = MFMA16(x0, wfr[gi][m][0], acc[nt]);
+                            acc[nt] = MFMA16(x1, wfr[gi][m][1], acc[nt]);
                         }
                     }
                 }
@@ -551,17 +527,14 @@ __global__ void __launch_bounds__(512) moka_xa_kernel(const XaArgs a) {
 // q+k+v 47.1 -> 34.4, gate+up 29.1 -> 24.9, down 49.5 -> 47.7; bit-identical slices.  Precondition: T % 16 == 0 (else the first form).
 // ------------------------------------------------------------------------------------------
 
-// HC = 2 (round 5, single projections): a split-K slice covers 1024 columns -- the workgroup takes the two 512-column halves of a tile as
-// two consecutive steps of the same ring, the accumulators stay in registers across them and the eight waves' partials are summed (and
-// the slice row written) once per TILE: half the slices for the consumers to re-sum (the fused up-projection sums them once per
-// column range of every token block), half the block reductions.  The weight fragments of both halves are resident (G = 1: 12 fragments).
-template <int G, int NS, int HC = 1>
+// (measured and lost, round 5: 1024-column slices for single projections -- both halves of a tile as two steps of the ring, 92 registers instead of 64)
+template <int G>
 __global__ void __launch_bounds__(512) moka_xs_kernel(const XaArgs a, int tiles_per_block) {
     const uint2 ep = drop_epoch(a.drop[0]);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int RP = 16, RPITCH = 1040, STAGE = 16 * RPITCH;   // bytes; pitch 260 dwords: the 64 lanes of a ds_read_b128 spread evenly over the banks
     constexpr int SLOT = 16 * RP;                                // floats per (wave, projection) partial tile
-    constexpr int KWS = 512 * HC;                                // columns per slice
+    constexpr int NS = 2;                                        // stages of the ring
     unsigned char* ring = smem;                                  // [NS][16 rows][RPITCH]
     float* slots = (float*)(smem + NS * STAGE);                  // [2][8][G][SLOT]
     unsigned char* smod = (unsigned char*)(slots + 2 * 8 * G * SLOT);
@@ -573,17 +546,15 @@ __global__ void __launch_bounds__(512) moka_xs_kernel(const XaArgs a, int tiles_
     const int t0 = blockIdx.y * tiles_per_block;
     const int nt = min(tiles_per_block, ntile_all - t0);
     if (nt <= 0) return;
-    const int nstep = nt * HC;                                   // a step = one 16-token x 512-column tile of the ring
-    const int cb0 = blockIdx.x * KWS, c0 = cb0 + 64 * wave;
+    const int cb0 = blockIdx.x * 512, c0 = cb0 + 64 * wave;
     for (int e = tid; e < nt * 16; e += 512) smod[e] = a.tok_mod[t0 * 16 + e];
 
     // producer side: wave w brings rows 2w and 2w+1 of every tile; lane l the 16 bytes at column cb0 + 8 l (clamped into the row)
     const unsigned ring_base = (unsigned)(size_t)ring;
-    auto issue = [&](int step) {
-        const int sl = min(step, nstep - 1);                     // past the run: re-request its last tile (L2 hit) -- every iteration issues the same count
-        const int st = step % NS;
-        const int tl = HC == 1 ? sl : sl >> 1;
-        const int ccol = min(cb0 + (HC == 1 ? 0 : 512 * (sl & 1)) + 8 * lane, a.C - 8);
+    auto issue = [&](int tile) {
+        const int tl = min(tile, nt - 1);                        // past the run: re-request its last tile (L2 hit) -- every iteration issues the same count
+        const int st = tile % NS;
+        const int ccol = min(cb0 + 8 * lane, a.C - 8);
 #pragma unroll
         for (int rr = 0; rr < 2; ++rr) {
             const int row = 2 * wave + rr;
@@ -591,36 +562,32 @@ __global__ void __launch_bounds__(512) moka_xs_kernel(const XaArgs a, int tiles_
             glds16(src, __builtin_amdgcn_readfirstlane(ring_base + st * STAGE + row * RPITCH));
         }
     };
-    // weights: the fragments of my 64 columns (of every half), all modalities / projections, resident (loads the compiler does not track:
+    // weights: the fragments of my 64 columns, all modalities / projections, resident (loads the compiler does not track:
     // explicit waits).  Requested FIRST (a wave's loads return in order and the weights are needed first), then the first NS-1 tiles.
-    bf16x8 wfr[HC][G][MOKA_MAX_MOD][2];
+    bf16x8 wfr[G][MOKA_MAX_MOD][2];
 #pragma unroll
-    for (int hf = 0; hf < HC; ++hf)
+    for (int gi = 0; gi < G; ++gi)
 #pragma unroll
-        for (int gi = 0; gi < G; ++gi)
+        for (int m = 0; m < MOKA_MAX_MOD; ++m)
 #pragma unroll
-            for (int m = 0; m < MOKA_MAX_MOD; ++m)
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk) {
-                    const int c = min(c0 + 512 * hf + 32 * kk + 8 * g, a.C - 8);
-                    const int mm = min(m, a.M - 1);
-                    const unsigned char* src = a.A[gi][mm] + ((size_t)min(i, a.r - 1) * a.C + c) * 2;
-                    wfr[hf][gi][m][kk] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
-                    asm volatile("global_load_dwordx4 %0, %1, off" : "+v"(wfr[hf][gi][m][kk]) : "v"(src) : "memory");
-                }
+            for (int kk = 0; kk < 2; ++kk) {
+                const int c = min(c0 + 32 * kk + 8 * g, a.C - 8);
+                const int mm = min(m, a.M - 1);
+                const unsigned char* src = a.A[gi][mm] + ((size_t)min(i, a.r - 1) * a.C + c) * 2;
+                wfr[gi][m][kk] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+                asm volatile("global_load_dwordx4 %0, %1, off" : "+v"(wfr[gi][m][kk]) : "v"(src) : "memory");
+            }
 #pragma unroll
     for (int t = 0; t < NS - 1; ++t) issue(t);
 #pragma unroll
-    for (int hf = 0; hf < HC; ++hf)
+    for (int gi = 0; gi < G; ++gi)
 #pragma unroll
-        for (int gi = 0; gi < G; ++gi)
+        for (int m = 0; m < MOKA_MAX_MOD; ++m)
 #pragma unroll
-            for (int m = 0; m < MOKA_MAX_MOD; ++m)
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk) {
-                    asm volatile("s_waitcnt vmcnt(%1)" : "+v"(wfr[hf][gi][m][kk]) : "n"(2 * (NS - 1)) : "memory");     // the weights have landed, the tiles are still on their way
-                    if (m >= a.M || c0 + 512 * hf + 32 * kk + 8 * g >= a.C) wfr[hf][gi][m][kk] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
-                }
+            for (int kk = 0; kk < 2; ++kk) {
+                asm volatile("s_waitcnt vmcnt(%1)" : "+v"(wfr[gi][m][kk]) : "n"(2 * (NS - 1)) : "memory");     // the weights have landed, the tiles are still on their way
+                if (m >= a.M || c0 + 32 * kk + 8 * g >= a.C) wfr[gi][m][kk] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+            }
 
     const bf16x8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
     auto reduce = [&](int k) {                                   // waves 0..3: sum the eight waves' partials of tile k, write the slice rows
@@ -639,13 +606,12 @@ __global__ void __launch_bounds__(512) moka_xs_kernel(const XaArgs a, int tiles_
         }
     };
     f32x4 acc[G];
-    for (int s = 0; s < nstep; ++s) {
-        const int k = HC == 1 ? s : s >> 1, hf = HC == 1 ? 0 : (s & 1);
+    for (int k = 0; k < nt; ++k) {
         asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" :: "n"(2 * (NS - 2)) : "memory");
-        if (s == 1) TRACE(1);
-        if (hf == 0 && k > 0) reduce(k - 1);
-        issue(s + NS - 1);
-        const unsigned char* stg = ring + (s % NS) * STAGE;
+        if (k == 1) TRACE(1);
+        if (k > 0) reduce(k - 1);
+        issue(k + NS - 1);
+        const unsigned char* stg = ring + (k % NS) * STAGE;
         bf16x8 xf[2];
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) xf[kk] = *(const bf16x8*)(stg + i * RPITCH + 128 * wave + 64 * kk + 16 * g);
@@ -654,10 +620,10 @@ __global__ void __launch_bounds__(512) moka_xs_kernel(const XaArgs a, int tiles_
         unsigned pm = 0;
 #pragma unroll
         for (int m = 0; m < MOKA_MAX_MOD; ++m) if (m < a.M && __any(mrow == m)) pm |= 1u << m;
-        const bool wactive = c0 + 512 * hf < a.C;
+        const bool wactive = c0 < a.C;
 #pragma unroll
         for (int gi = 0; gi < G; ++gi) {
-            if (hf == 0) acc[gi] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            acc[gi] = (f32x4){0.f, 0.f, 0.f, 0.f};
             if (wactive && pm) {
                 bf16x8 xg[2];
 #pragma unroll
@@ -665,26 +631,19 @@ __global__ void __launch_bounds__(512) moka_xs_kernel(const XaArgs a, int tiles_
                     xg[kk] = xf[kk];
                     if (a.drop[gi].thr) {
                         const unsigned trow = (unsigned)((t0 + k) * 16 + i);
-                        xg[kk] = drop_apply(xg[kk], drop_keep8(a.drop[gi], ep, trow * (unsigned)(a.C >> 3) + (unsigned)((c0 + 512 * hf + 32 * kk) >> 3) + (unsigned)g));
+                        xg[kk] = drop_apply(xg[kk], drop_keep8(a.drop[gi], ep, trow * (unsigned)(a.C >> 3) + (unsigned)((c0 + 32 * kk) >> 3) + (unsigned)g));
                     }
                 }
 #pragma unroll
                 for (int m = 0; m < MOKA_MAX_MOD; ++m) {
                     if (!(pm & (1u << m))) continue;
                     const bool other = (pm != (1u << m)) && mrow != m;
-                    if (HC == 1 || hf == 0) {
-                        acc[gi] = MFMA16(wfr[0][gi][m][0], other ? z8 : xg[0], acc[gi]);
-                        acc[gi] = MFMA16(wfr[0][gi][m][1], other ? z8 : xg[1], acc[gi]);
-                    } else {
-                        acc[gi] = MFMA16(wfr[HC - 1][gi][m][0], other ? z8 : xg[0], acc[gi]);
-                        acc[gi] = MFMA16(wfr[HC - 1][gi][m][1], other ? z8 : xg[1], acc[gi]);
-                    }
+                    acc[gi] = MFMA16(wfr[gi][m][0], other ? z8 : xg[0], acc[gi]);
+                    acc[gi] = MFMA16(wfr[gi][m][1], other ? z8 : xg[1], acc[gi]);
                 }
             }
-            if (hf == HC - 1) {
-                MFMA_SETTLE(acc[gi]);
-                *(f32x4*)(myslot + (size_t)gi * SLOT + i * RP + 4 * g) = acc[gi];
-            }
+            MFMA_SETTLE(acc[gi]);
+            *(f32x4*)(myslot + (size_t)gi * SLOT + i * RP + 4 * g) = acc[gi];
         }
     }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -695,137 +654,11 @@ __global__ void __launch_bounds__(512) moka_xs_kernel(const XaArgs a, int tiles_
 
 
 // ------------------------------------------------------------------------------------------
-// F (second form): the same down-projection with INDEPENDENT waves.  Block = 8 waves on a [16 * sub_per_block tokens x KW
-// columns] tile (KW = 512, or 256 for rank pad 64); a wave takes whole 16-token sub-tiles (all KW columns of the slice), so its
-// [RP x 16] result is complete in its accumulators and goes straight to the split-K slice -- no per-wave partials in LDS, no
-// block reduction, no barrier in the stream (the first form pays two barriers and a 512-thread sum every two groups, with one or
-// two lock-stepped blocks per CU).  The weight fragments cannot stay in registers this way (KW / 32 K steps x modalities x
-// projections); the fragments of the modalities that occur in the block's token run are staged ONCE per block into LDS in
-// MFMA-fragment order (KW / 32 KB per modality, projection and rank tile) and read back with one conflict-free ds_read_b128 per
-// MFMA.  D^T orientation (A = weights, B = x): a lane ends up with 4 consecutive ranks of ONE token -> one 16-byte store per
-// lane and rank tile.
-// ------------------------------------------------------------------------------------------
-template <int RP, int G, int KW>
-__global__ void __launch_bounds__(512, (G * (RP / 16) >= 3) ? 2 : 4) moka_xw_kernel(const XaArgs a, int sub_per_block) {
-    const uint2 ep = drop_epoch(a.drop[0]);
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int NT = RP / 16, NKS = KW / 32, HK = 4, NU = NKS / HK;     // a sub-tile streams in NU units of HK K steps (two units in flight)
-    constexpr int FR = NKS * 64;                             // 16-byte fragments of one (modality, projection, rank tile)
-    static_assert(NU % 2 == 0, "units alternate between two buffers");
-    bf16x8* wl = (bf16x8*)smem;                              // [M][G][NT][NKS][64]
-    __shared__ unsigned s_wpm[8];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i = lane & 15, g = lane >> 4;
-    const int nsub = (a.T + 15) >> 4;
-    const int sb0 = blockIdx.y * sub_per_block, sb1 = min(nsub, sb0 + sub_per_block);
-    if (sb0 >= nsub) return;
-    const int cb0 = blockIdx.x * KW;
-    const int nks = min(NKS, (a.C - cb0) >> 5);              // K steps of this column slice (C % 32 == 0)
-    const int nj = (sb1 - sb0 - wave + 7) >> 3;              // my sub-tiles: sb0 + wave, + 8, ...   (may be <= 0 on a ragged end)
-    const int sub_last = sb0 + wave + 8 * (max(nj, 1) - 1);  // prefetches behind my last sub-tile re-request it (L2 hit)
-    const bf16x8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
-
-    bf16x8 xA[HK], xB[HK];
-    auto issue = [&](bf16x8 (&xb)[HK], int sub_, int half) {
-        const int sub = min(min(sub_, sub_last), nsub - 1);
-        const unsigned char* row = a.x + (size_t)min(16 * sub + i, a.T - 1) * a.C * 2;
-#pragma unroll
-        for (int q = 0; q < HK; ++q) xb[q] = *(const bf16x8*)(row + (size_t)min(cb0 + 32 * (HK * half + q) + 8 * g, a.C - 8) * 2);
-    };
-    issue(xA, sb0 + wave, 0);                                // the x stream starts before the weights are staged
-
-    // modalities of the block's token run -> staged into LDS
-    {
-        unsigned bits = 0;
-        if (tid < (sb1 - sb0) * 16) {
-            const int m = a.tok_mod[sb0 * 16 + tid];
-            if (m < a.M) bits = 1u << m;
-        }
-        unsigned wb = 0;
-#pragma unroll
-        for (int m = 0; m < MOKA_MAX_MOD; ++m) if (__any((bits >> m) & 1u)) wb |= 1u << m;
-        if (lane == 0) s_wpm[wave] = wb;
-    }
-    __syncthreads();
-    unsigned pmB = 0;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) pmB |= s_wpm[w];
-    if (pmB == 0) return;                                    // a run of padding only: nothing to write (block uniform)
-    for (int m = 0; m < a.M; ++m) {
-        if (!(pmB & (1u << m))) continue;
-        for (int e = tid; e < G * NT * FR; e += 512) {
-            const int ln = e & 63, ks = (e >> 6) % NKS, nt = (e / FR) % NT, gi = e / (FR * NT);
-            bf16x8 v = z8;
-            // rank rows >= r do not exist: clamp the row, the result rows are zeroed when the slice is written
-            if (ks < nks) v = *(const bf16x8*)(a.A[gi][m] + ((size_t)min(nt * 16 + (ln & 15), a.r - 1) * a.C + cb0 + 32 * ks + 8 * (ln >> 4)) * 2);
-            wl[(size_t)m * G * NT * FR + e] = v;
-        }
-    }
-    __syncthreads();
-
-    for (int j = 0; j < nj; ++j) {
-        const int sub = sb0 + wave + 8 * j;
-        issue(xB, sub, 1);
-        const int mrow = a.tok_mod[16 * sub + i];            // padded past T with MOKA_MOD_NONE
-        unsigned pm = 0;
-#pragma unroll
-        for (int m = 0; m < MOKA_MAX_MOD; ++m) if (m < a.M && __any(mrow == m)) pm |= 1u << m;
-        const bool mixed = (pm & (pm - 1)) != 0;             // span boundary inside the 16 tokens (wave uniform)
-        f32x4 acc[G][NT];
-#pragma unroll
-        for (int gi = 0; gi < G; ++gi)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc[gi][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        const unsigned trow = (unsigned)min(16 * sub + i, a.T - 1);
-        // one MFMA chain per modality present; in a mixed sub-tile my token only counts in the chain of its own modality.  The
-        // fragment reads of step q + 1 overlap the multiplies of step q (the sched barriers keep the compiler from hoisting all reads).
-        auto compute = [&](bf16x8 (&xb)[HK], int half) {
-#pragma unroll
-            for (int q = 0; q < HK; ++q) {
-                const int ks = HK * half + q;
-                const bf16x8 xq = (ks < nks) ? xb[q] : z8;  // branch-free: a slice of a ragged width has fewer K steps
-#pragma unroll
-                for (int gi = 0; gi < G; ++gi) {
-                    bf16x8 xg = xq;
-                    if (a.drop[gi].thr) xg = drop_apply(xg, drop_keep8(a.drop[gi], ep, trow * (unsigned)(a.C >> 3) + (unsigned)((cb0 + 32 * ks) >> 3) + (unsigned)g));
-#pragma unroll
-                    for (int m = 0; m < MOKA_MAX_MOD; ++m) {
-                        if (!(pm & (1u << m))) continue;     // wave uniform
-                        const bf16x8 xm = (!mixed || mrow == m) ? xg : z8;
-#pragma unroll
-                        for (int nt = 0; nt < NT; ++nt)
-                            acc[gi][nt] = MFMA16(wl[(((size_t)m * G + gi) * NT + nt) * FR + ks * 64 + lane], xm, acc[gi][nt]);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        };
-#pragma unroll
-        for (int u = 0; u < NU; u += 2) {
-            if (u) issue(xB, sub, u + 1);
-            if (pm) compute(xA, u);
-            if (u + 2 < NU) issue(xA, sub, u + 2); else issue(xA, sub + 8, 0);
-            if (pm) compute(xB, u + 1);
-        }
-        if (pm) {
-            const float sc = mod_scale(a.s_mod, mrow);       // 0 for tokens of no modality
-            const int t = 16 * sub + i;
-#pragma unroll
-            for (int gi = 0; gi < G; ++gi)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    MFMA_SETTLE(acc[gi][nt]);
-                    f32x4 v;
-#pragma unroll
-                    for (int reg = 0; reg < 4; ++reg) v[reg] = (16 * nt + 4 * g + reg < a.r && mrow < a.M) ? acc[gi][nt][reg] * sc : 0.f;
-                    if (t < a.T) *(f32x4*)(a.part[gi] + ((size_t)blockIdx.x * a.T + t) * RP + 16 * nt + 4 * g) = v;
-                }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// F (rank pad 64): independent waves as above, but a workgroup keeps its 8 sub-tiles (128 tokens, one per wave) and walks `cps`
+// F (rank pads 32 / 64): the same down-projection with INDEPENDENT waves: a wave takes a whole 16-token sub-tile, so its [RP x 16] result is
+// complete in its accumulators and goes straight to the split-K slice -- no per-wave partials in LDS, no block reduction (the first form pays
+// two barriers and a 512-thread sum every two groups).  The weight fragments cannot stay in registers this way; they are staged into LDS in
+// MFMA-fragment order and read back with one conflict-free ds_read_b128 per MFMA.  D^T orientation (A = weights, B = x): a lane ends up with 4
+// consecutive ranks of ONE token -> one 16-byte store per lane and rank tile.  A workgroup keeps its 8 sub-tiles (128 tokens, one per wave) and walks `cps`
 // consecutive 256-column chunks with the accumulators in registers: one split-K slice per cps chunks instead of one per chunk.  At
 // rank 64 a slice row is 256 bytes -- with one slice per 256 columns the forward WROTE half as many bytes as it read (and the
 // interaction kernel read them back: 20 slices of 2 MB per 5120-wide projection); with the slices sized so that the grid gives every CU
@@ -987,9 +820,9 @@ __global__ void __launch_bounds__(512, G > 1 ? 2 : 4) moka_xwm_kernel(const XaBa
 // launch helpers (host)
 // ------------------------------------------------------------------------------------------
 #define det_finish mk_det_finish
-template <int RP, bool WITH_DB, int NG, int KK = 2>
+template <bool WITH_DB, int NG>
 static void launch_gy_t(const GyBatch& gb, int nz, int ncb, hipStream_t st) {
-    constexpr int PH = (RP == 64) ? 1 : 2;
+    constexpr int RP = 16, PH = 2;
     const int ntb = ((gb.z[0].Tp >> 5) + NG - 1) / NG;
     const size_t lds = (WITH_DB ? (size_t)8 * (32 * 160) : 0) + (size_t)8 * PH * 32 * RP * 4;
     SumRunsArgs sr;
@@ -1008,7 +841,7 @@ static void launch_gy_t(const GyBatch& gb, int nz, int ncb, hipStream_t st) {
         }
     }
     GyBatch& gx = const_cast<GyBatch&>(gb);              // (the caller's own copy)
-    constexpr int BCOL = 256 * KK;
+    constexpr int BCOL = 512;
     int xtot = 0;
     for (int z = 0; z < MOKA_MAX_GROUP; ++z) {
         if (z < nz) {
@@ -1019,12 +852,12 @@ static void launch_gy_t(const GyBatch& gb, int nz, int ncb, hipStream_t st) {
     }
     gx.ncb_max = ncb;
     if (det) {
-        ensure_lds((const void*)moka_gy_kernel<RP, WITH_DB, NG, WITH_DB, KK>, lds);
-        hipLaunchKernelGGL((moka_gy_kernel<RP, WITH_DB, NG, WITH_DB, KK>), dim3(xtot, ntb, 1), dim3(512), lds, st, gb);
+        ensure_lds((const void*)moka_gy_kernel<WITH_DB, NG, WITH_DB>, lds);
+        hipLaunchKernelGGL((moka_gy_kernel<WITH_DB, NG, WITH_DB>), dim3(xtot, ntb, 1), dim3(512), lds, st, gb);
         det_finish(sr, st);
     } else {
-        ensure_lds((const void*)moka_gy_kernel<RP, WITH_DB, NG, false, KK>, lds);
-        hipLaunchKernelGGL((moka_gy_kernel<RP, WITH_DB, NG, false, KK>), dim3(xtot, ntb, 1), dim3(512), lds, st, gb);
+        ensure_lds((const void*)moka_gy_kernel<WITH_DB, NG, false>, lds);
+        hipLaunchKernelGGL((moka_gy_kernel<WITH_DB, NG, false>), dim3(xtot, ntb, 1), dim3(512), lds, st, gb);
     }
 }
 
@@ -1043,7 +876,6 @@ static void launch_gs_t(const GyBatch& gb, int nz, int ncb, int ng, hipStream_t 
         gx.xend[z] = xtot;
     }
     gx.ncb_max = ncb;
-    gx.dbg = g_tune_gs_dbg;
     SumRunsArgs sr;
     bool det = false;
     const int ntb_static = (ngroups + ng - 1) / ng;
@@ -1085,97 +917,73 @@ static int launch_gs_auto(GyBatch& gb, int nz, int Cmax, hipStream_t st) {
     // once per run), 64 long workgroups while the other chain's launch has the rest of the chip: r = 32, two chains of 4096 tokens, 38.38 -> 37.92 ms per step (three
     // alternating pairs; the pass alone gets slower, 13.55 -> 14.99 ms); rank pad 16: no difference (29.61 / 29.64 ms), left alone; 32 groups lose at both ranks
     if (RP == 32 && t_company > 1 && ng < 16 && 2 * blocks(16) >= cus) ng = 16;
-    if (g_tune_gy_ng > 0) ng = g_tune_gy_ng;
     launch_gs_t<RP, WITH_DB>(gb, nz, (Cmax + 511) / 512, ng, st);
     return check_launch("moka_gs_kernel");
 }
 
-static int bwd_kw(int T, int C, int r);
-template <int RP, bool WITH_DB>
-static int launch_gy_rp(const GyBatch& gb_in, int nz, int Cmax, hipStream_t st) {
-    GyBatch gb = gb_in;                                  // (launch_gy_t fills in the grid map)
-    // LDS-DMA ring; at r <= 16 except for the widest batches on long token sets (gate + up, 2 x 11008, 8192 tokens: 97.5 against 92.8 us for
-    // the first form in the step's kernel sequence; o / down 26.3 against 27.9, q + k + v 54 against 58; on 4096-token launches -- the part-batch
-    // chains of round 5 -- the ring wins there too: up_bwd 8.48 -> 8.18 ms per pass, step 30.3 -> 29.95 ms); "gy_form" 1 / 2 forces the first / second form
-    if constexpr (RP <= 32) {
-        if (g_tune_gy_form == 2 || (g_tune_gy_form == 0 && (RP == 32 || !(nz > 1 && Cmax > 8192 && gb.z[0].T > 4096)))) return launch_gs_auto<RP, WITH_DB>(gb, nz, Cmax, st);
+// rank pad 64 (g only): the chunk-walk kernel of the forward with one weight set (moka_xwm_kernel<64, true, 1>)
+static int launch_gy_xwm(const GyBatch& gb, int nz, int Cmax, hipStream_t st) {
+    const int T = gb.z[0].T;
+    const int kw = bwd_kw(T, Cmax, gb.z[0].r), ks = (Cmax + kw - 1) / kw;
+    XaBatch xb;
+    memset(&xb, 0, sizeof(xb));
+    for (int z = 0; z < nz; ++z) {
+        const GyArgs& ga = gb.z[z];
+        XaArgs& xa = xb.z[z];
+        xa.x = ga.gy; xa.tok_mod = ga.tok_mod; xa.T = T; xa.C = ga.C; xa.r = ga.r; xa.M = ga.M;
+        xa.part[0] = ga.g_part;
+        xa.drop[0].inv_keep = 1.f;
+        for (int m = 0; m < MOKA_MAX_MOD; ++m) { xa.s_mod[m] = ga.s_mod[m]; xa.A[0][m] = ga.BwT; }
     }
-    if constexpr (RP == 64 && !WITH_DB) {
-        if (g_tune_gy_form != 1) {
-            // the chunk-walk kernel of the forward with one weight set (moka_xwm_kernel<64, true, 1>): a launch per projection
-            const int T = gb.z[0].T;
-            const int kw = bwd_kw(T, Cmax, gb.z[0].r), ks = (Cmax + kw - 1) / kw;
-            XaBatch xb;
-            memset(&xb, 0, sizeof(xb));
-            for (int z = 0; z < nz; ++z) {
-                const GyArgs& ga = gb.z[z];
-                XaArgs& xa = xb.z[z];
-                xa.x = ga.gy; xa.tok_mod = ga.tok_mod; xa.T = T; xa.C = ga.C; xa.r = ga.r; xa.M = ga.M;
-                xa.part[0] = ga.g_part;
-                xa.drop[0].inv_keep = 1.f;
-                for (int m = 0; m < MOKA_MAX_MOD; ++m) { xa.s_mod[m] = ga.s_mod[m]; xa.A[0][m] = ga.BwT; }
-            }
-            // ONE launch for the group (grid z): a narrower member's workgroups beyond its own slices find no chunk to walk and write zeros
-            // (the interaction backward sums ks slices for every member)
-            const size_t lds = (size_t)4 * 8 * 1024;
-            ensure_lds((const void*)moka_xwm_kernel<64, true, 1>, lds);
-            hipLaunchKernelGGL((moka_xwm_kernel<64, true, 1>), dim3(ks, (T + 127) / 128, nz), dim3(512), lds, st, xb, kw / 256);
-            return check_launch("moka_xwm_kernel");
-        }
-        // rank pad 64: 128 columns per wave, one split-K slice per 1024 columns (bwd_kw): the rank-space backward reads half as many
-        // slices (7.2 -> 6.3 ms per step); this pass itself is unchanged (150-166 VGPRs leave one block per CU where 95 left two,
-        // which cancels the halved eight-wave sums; capped at 128 registers it spills and loses 9 ms)
-        const int ncb4 = (Cmax + 1023) / 1024;
-        const int ngroups4 = gb.z[0].Tp >> 5;
-        const long b4 = (long)ncb4 * nz * ((ngroups4 + 3) / 4);
-        if (g_tune_gy_ng == 2 || (g_tune_gy_ng == 0 && b4 < 2L * num_cu())) launch_gy_t<64, false, 2, 4>(gb, nz, ncb4, st);
-        else launch_gy_t<64, false, 4, 4>(gb, nz, ncb4, st);
-        return check_launch("moka_gy_kernel");
-    }
-    const int ncb = (Cmax + 511) / 512;
-    const int ngroups = gb.z[0].Tp >> 5;
-    // groups per block: without dB short runs (more blocks); with dB the longest run that still gives every CU a block
-    // (measured at T = 8192: 4096 wide -> 8, 11008 wide -> 8, 3 x 4096 -> 8/16, 2 x 11008 -> 16; g only -> 4)
-    int ng = 4;
-    if (WITH_DB) {
-        long active = 0;                                    // column blocks that do work (narrower batch members: see launch_expand_t)
-        for (int z = 0; z < nz; ++z) active += (gb.z[z].C + 511) / 512;
-        auto blocks = [&](int n) { return active * ((ngroups + n - 1) / n); };
-        ng = blocks(16) >= 2L * num_cu() ? 16 : (blocks(8) >= (long)num_cu() ? 8 : 4);
-    }
-    if (g_tune_gy_ng == 4 || g_tune_gy_ng == 8 || g_tune_gy_ng == 16) ng = g_tune_gy_ng;
-    if (ng == 16) launch_gy_t<RP, WITH_DB, 16>(gb, nz, ncb, st);
-    else if (ng == 8) launch_gy_t<RP, WITH_DB, 8>(gb, nz, ncb, st);
-    else launch_gy_t<RP, WITH_DB, 4>(gb, nz, ncb, st);
-    return check_launch("moka_gy_kernel");
+    // ONE launch for the group (grid z): a narrower member's workgroups beyond its own slices find no chunk to walk and write zeros
+    // (the interaction backward sums ks slices for every member)
+    // (measured and lost: the register-staged form with 128 columns per wave and 1024-column slices -- 150-166 VGPRs, one block per CU)
+    const size_t lds = (size_t)4 * 8 * 1024;
+    ensure_lds((const void*)moka_xwm_kernel<64, true, 1>, lds);
+    hipLaunchKernelGGL((moka_xwm_kernel<64, true, 1>), dim3(ks, (T + 127) / 128, nz), dim3(512), lds, st, xb, kw / 256);
+    return check_launch("moka_xwm_kernel");
 }
 
 template <bool WITH_DB>
-static int launch_gy(const GyBatch& gb, int nz, int Cmax, int RP, hipStream_t st) {
-    if (RP == 16) return launch_gy_rp<16, WITH_DB>(gb, nz, Cmax, st);
-    if constexpr (WITH_DB) {                             // rank pad 32: only the LDS-DMA form carries dB along
-        if (RP != 32) return fail(MOKA_EINVAL, "moka_up_bwd: the one-pass g + dB kernels are built for r <= 32 only");
-        GyBatch g2 = gb;
-        return launch_gs_auto<32, true>(g2, nz, Cmax, st);
-    } else {
-        if (RP == 32) return launch_gy_rp<32, false>(gb, nz, Cmax, st);
-        return launch_gy_rp<64, false>(gb, nz, Cmax, st);
+static int launch_gy(const GyBatch& gb_in, int nz, int Cmax, int RP, hipStream_t st) {
+    GyBatch gb = gb_in;                                  // (the launch helpers fill in the grid map)
+    if (RP == 64) {
+        if constexpr (WITH_DB) return fail(MOKA_EINVAL, "moka_up_bwd: the one-pass g + dB kernels are built for r <= 32 only");
+        else return launch_gy_xwm(gb, nz, Cmax, st);
     }
+    if (RP == 32) return launch_gs_auto<32, WITH_DB>(gb, nz, Cmax, st);
+    // r <= 16: the LDS-DMA ring, except for the widest batches on long token sets (gate + up, 2 x 11008, 8192 tokens: 97.5 against 92.8 us for
+    // the first form in the step's kernel sequence; o / down 26.3 against 27.9, q + k + v 54 against 58; on 4096-token launches -- the part-batch
+    // chains of round 5 -- the ring wins there too: up_bwd 8.48 -> 8.18 ms per pass, step 30.3 -> 29.95 ms)
+    if (!(nz > 1 && Cmax > 8192 && gb.z[0].T > 4096)) return launch_gs_auto<16, WITH_DB>(gb, nz, Cmax, st);
+    const int ncb = (Cmax + 511) / 512;
+    // groups per block: without dB short runs (more blocks); with dB the longest run that still gives every CU a block
+    // (measured at T = 8192: 4096 wide -> 8, 11008 wide -> 8, 3 x 4096 -> 8/16, 2 x 11008 -> 16; g only -> 4)
+    if constexpr (WITH_DB) {
+        const int ngroups = gb.z[0].Tp >> 5;
+        long active = 0;                                    // column blocks that do work (narrower batch members: see launch_expand_t)
+        for (int z = 0; z < nz; ++z) active += (gb.z[z].C + 511) / 512;
+        // (never fewer than 8: this branch has >= 18 active column blocks and >= 129 token groups, i.e. >= 306 workgroups of 8 groups,
+        //  more than a gfx950 has CUs)
+        if (active * ((ngroups + 15) / 16) >= 2L * num_cu()) launch_gy_t<true, 16>(gb, nz, ncb, st);
+        else launch_gy_t<true, 8>(gb, nz, ncb, st);
+    } else launch_gy_t<false, 4>(gb, nz, ncb, st);
+    return check_launch("moka_gy_kernel");
 }
 
-template <int RP, int G, int NG>
+template <int G, int NG>
 static void launch_xa_t(const XaArgs& a, hipStream_t st) {
-    constexpr int PH = 2;
+    constexpr int RP = 16, PH = 2;
     const int ncb = (a.C + 511) / 512, ntb = (((a.T + 31) >> 5) + NG - 1) / NG;
     const size_t lds = (size_t)8 * PH * G * 32 * RP * 4;
-    ensure_lds((const void*)moka_xa_kernel<RP, G, NG>, lds);
-    hipLaunchKernelGGL((moka_xa_kernel<RP, G, NG>), dim3(ncb, ntb), dim3(512), lds, st, a);
+    ensure_lds((const void*)moka_xa_kernel<G, NG>, lds);
+    hipLaunchKernelGGL((moka_xa_kernel<G, NG>), dim3(ncb, ntb), dim3(512), lds, st, a);
 }
 
-template <int G, int HC = 1>
+template <int G>
 static int launch_xs(const XaArgs& a, hipStream_t st) {
     constexpr int NS = 2;
-    const int ncb = (a.C + 512 * HC - 1) / (512 * HC), ntile = a.T >> 4;
+    const int ncb = (a.C + 511) / 512, ntile = a.T >> 4;
     // tiles per workgroup: long runs amortise the resident weights (G x 6 KB per wave), short ones give more workgroups
     int tpb = (G == 3) ? 16 : 8;
     // (three projections: one workgroup of 16 tiles per CU beat two of 8 -- 34.4 vs 40.0 us -- their 18 KB of weights per wave are the start-up;
@@ -1183,44 +991,19 @@ static int launch_xs(const XaArgs& a, hipStream_t st) {
     //  7B widths, step 29.43 -> 29.12, 29.29 -> 29.24 ms; 8192-token launches keep their 512 workgroups of 8 tiles either way)
     while (tpb > 2 && (long)ncb * ((ntile + tpb - 1) / tpb) < (long)num_cu()) tpb >>= 1;
     const size_t lds = (size_t)NS * 16 * 1040 + (size_t)2 * 8 * G * 256 * 4 + (size_t)tpb * 16;
-    ensure_lds((const void*)moka_xs_kernel<G, NS, HC>, lds);
-    hipLaunchKernelGGL((moka_xs_kernel<G, NS, HC>), dim3(ncb, (ntile + tpb - 1) / tpb), dim3(512), lds, st, a, tpb);
+    ensure_lds((const void*)moka_xs_kernel<G>, lds);
+    hipLaunchKernelGGL((moka_xs_kernel<G>), dim3(ncb, (ntile + tpb - 1) / tpb), dim3(512), lds, st, a, tpb);
     return check_launch("moka_xs_kernel");
-}
-
-template <int RP, int G>
-static int launch_xw(const XaArgs& a, hipStream_t st) {
-    constexpr int KW = (RP == 64) ? 256 : 512;               // LDS budget: M x G x RP/16 x KW/32 KB of weight fragments
-    const int nsub = (a.T + 15) / 16;
-    const int ncb = (a.C + KW - 1) / KW;
-    // sub-tiles per block: long runs amortise the weight staging, short ones give more blocks
-    int spb = (g_tune_xa_ng > 0) ? 2 * g_tune_xa_ng : 16;
-    while (spb > 8 && (long)ncb * ((nsub + spb - 1) / spb) < 2L * num_cu()) spb >>= 1;
-    const size_t lds = (size_t)MOKA_MAX_MOD * G * (RP / 16) * (KW / 32) * 1024;
-    ensure_lds((const void*)moka_xw_kernel<RP, G, KW>, lds);
-    hipLaunchKernelGGL((moka_xw_kernel<RP, G, KW>), dim3(ncb, (nsub + spb - 1) / spb), dim3(512), lds, st, a, spb);
-    return check_launch("moka_xw_kernel");
-}
-
-// r > 16: one projection per launch (G x 3 x 2 x RP/16 resident weight fragments do not fit for G > 1)
-template <int RP>
-static int launch_xa_wide(const XaArgs& a, hipStream_t st) {
-    // 3 x 2 x RP/16 resident weight fragments per wave: RP = 64 needs long token runs to amortise them (41 -> 37 us at 4096)
-    const int ng = (g_tune_xa_ng == 2 || g_tune_xa_ng == 4 || g_tune_xa_ng == 8) ? g_tune_xa_ng : (RP == 64 ? 8 : 4);
-    if (ng == 2) launch_xa_t<RP, 1, 2>(a, st);
-    else if (ng == 8) launch_xa_t<RP, 1, 8>(a, st);
-    else launch_xa_t<RP, 1, 4>(a, st);
-    return check_launch("moka_xa_kernel");
 }
 
 template <int G>
 static int launch_xa(const XaArgs& a, hipStream_t st) {
     // groups per block (measured at T = 8192): three projections amortise their 18 resident weight fragments over longer runs,
     // a wide single projection prefers more, shorter blocks
-    const int ng = (g_tune_xa_ng == 2 || g_tune_xa_ng == 4 || g_tune_xa_ng == 8) ? g_tune_xa_ng : (G == 3 ? 8 : ((G == 1 && a.C > 8192) ? 2 : 4));
-    if (ng == 2) launch_xa_t<16, G, 2>(a, st);
-    else if (ng == 8) launch_xa_t<16, G, 8>(a, st);
-    else launch_xa_t<16, G, 4>(a, st);
+    if constexpr (G == 3) launch_xa_t<3, 8>(a, st);
+    else if constexpr (G == 2) launch_xa_t<2, 4>(a, st);
+    else if (a.C > 8192) launch_xa_t<1, 2>(a, st);
+    else launch_xa_t<1, 4>(a, st);
     return check_launch("moka_xa_kernel");
 }
 
@@ -1248,19 +1031,12 @@ static int launch_xwm(const XaArgs& xa, int G, int kw, hipStream_t st) {
 
 #undef det_finish
 int mk_launch_gy(bool with_db, const GyBatch& gb, int nz, int Cmax, int RP, hipStream_t st) { return with_db ? launch_gy<true>(gb, nz, Cmax, RP, st) : launch_gy<false>(gb, nz, Cmax, RP, st); }
-int mk_launch_down_fwd(const XaArgs& xa, int G, int per_launch, int RP, int T, int d_in, int r, bool xwm32, hipStream_t stream) {
-    int rc;
-    if (use_xw(RP)) {                                    // independent waves, weights staged in LDS
-        if (RP == 16) rc = G == 1 ? launch_xw<16, 1>(xa, stream) : (G == 2 ? launch_xw<16, 2>(xa, stream) : launch_xw<16, 3>(xa, stream));
-        else if (RP == 32 && !xwm32) rc = launch_xw<32, 1>(xa, stream);
-        else if (RP == 64 && fwd_kw(T, d_in, r) == 256 && g_tune_xa_form == 3) rc = launch_xw<64, 1>(xa, stream);
-        else if (RP == 32) rc = launch_xwm<32>(xa, per_launch, fwd_kw(T, d_in, r), stream);
-        else rc = launch_xwm<64>(xa, per_launch, fwd_kw(T, d_in, r), stream);
-    } else
-    if (RP == 16 && (T & 15) == 0 && g_tune_xa_form != 1)    // LDS-DMA ring (whole 16-token tiles; "xa_form" 1 forces the first form)
-        rc = G == 1 ? (xs_wide(T, r, 1) ? launch_xs<1, 2>(xa, stream) : launch_xs<1>(xa, stream))
-                    : (G == 2 ? launch_xs<2>(xa, stream) : launch_xs<3>(xa, stream));
-    else if (RP == 16) rc = G == 1 ? launch_xa<1>(xa, stream) : (G == 2 ? launch_xa<2>(xa, stream) : launch_xa<3>(xa, stream));
-    else rc = RP == 32 ? launch_xa_wide<32>(xa, stream) : launch_xa_wide<64>(xa, stream);
-    return rc;
+int mk_launch_down_fwd(const XaArgs& xa, int G, int RP, hipStream_t stream) {
+    if (use_xw(RP)) {                                    // rank pads 32 / 64: the chunk-walk kernel, weights staged in LDS
+        const int kw = fwd_kw(xa.T, xa.C, xa.r);
+        return RP == 32 ? launch_xwm<32>(xa, G, kw, stream) : launch_xwm<64>(xa, G, kw, stream);
+    }
+    if ((xa.T & 15) == 0)                                // LDS-DMA ring (whole 16-token tiles)
+        return G == 1 ? launch_xs<1>(xa, stream) : (G == 2 ? launch_xs<2>(xa, stream) : launch_xs<3>(xa, stream));
+    return G == 1 ? launch_xa<1>(xa, stream) : (G == 2 ? launch_xa<2>(xa, stream) : launch_xa<3>(xa, stream));
 }

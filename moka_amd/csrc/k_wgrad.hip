@@ -7,10 +7,10 @@
 // OUT_CK (dB): blockIdx.z selects one of the batched problems.
 // !OUT_CK (dA) with G > 1: the G entries share `in` (= x) and the routing; wave set g of a block works on entry g.
 
-// Block = NW waves owning NSB*64 columns for a long run of tokens.  Each wave walks over a contiguous
+// Block = NW waves owning 64 columns for a long run of tokens.  Each wave walks over a contiguous
 // run of 32-token groups with a 2-deep software pipeline: tok_mod of group i+2 and the
-// [32 tokens][NSB*64 columns] tile + pack fragments of group i+1 are in flight while group i goes,
-// 64 columns at a time, through a wave-private 5 KB LDS region and is read back transposed
+// [32 tokens][64 columns] tile + pack fragments of group i+1 are in flight while group i goes,
+// through a wave-private 5 KB LDS region and is read back transposed
 // (ds_read_b64_tr_b16) as the MFMA A operand (rows = columns of `in`, K = tokens); B operand = the
 // rank-major pack of each modality present (masked planes: a plane only carries its own tokens).
 // One accumulator set per modality, so span boundaries cost nothing but an extra MFMA chain.
@@ -20,15 +20,15 @@
 // same token runs against the packs / accumulators of projection g.  The G waves of a run request the
 // same x lines within a short time, so the copies are served by L1 / L2 (hit-on-miss) and HBM sees
 // each line once; per-wave registers and LDS stay those of the single-projection kernel.
-template <int RP, int NSB, int NW, bool OUT_CK, int G, bool DET>
+template <int RP, int NW, bool OUT_CK, int G, bool DET>
 __global__ void __launch_bounds__(NW * G * 64) moka_wgrad_kernel(const WgradBatch ab) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int NT = RP / 16;
     constexpr int NM = OUT_CK ? 1 : MOKA_MAX_MOD;   // dB: one plane; dA: one plane per modality
     constexpr int CT = 4;                           // 16-column tiles per 64-column sub-tile
-    constexpr int CCB = NSB * 64;                   // columns per block
+    constexpr int CCB = 64;                         // columns per block
     constexpr int PITCH = 64 * 2 + 32;              // bytes per LDS row; odd multiple of 32
-    constexpr int REGION = NSB * 32 * PITCH;
+    constexpr int REGION = 32 * PITCH;
     const int tid = threadIdx.x, lane = tid & 63, wave_all = tid >> 6;
     const int gi = (G == 1) ? 0 : __builtin_amdgcn_readfirstlane(wave_all / NW);   // projection of this wave set
     const int wave = (G == 1) ? wave_all : wave_all - gi * NW;                        // token-run index inside the block
@@ -54,15 +54,13 @@ __global__ void __launch_bounds__(NW * G * 64) moka_wgrad_kernel(const WgradBatc
     TRACE_DECL(2);
     TRACE(0);
 
-    f32x4 acc[NM][NSB][CT][NT];
+    f32x4 acc[NM][CT][NT];
 #pragma unroll
     for (int m = 0; m < NM; ++m)
 #pragma unroll
-        for (int sb = 0; sb < NSB; ++sb)
+        for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc[m][sb][ct][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            for (int nt = 0; nt < NT; ++nt) acc[m][ct][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     unsigned ever = 0;
 
     auto present_of = [&](int mym) -> unsigned {
@@ -84,41 +82,35 @@ __global__ void __launch_bounds__(NW * G * 64) moka_wgrad_kernel(const WgradBatc
     // Always issued (group index clamped): a conditionally issued load makes the vmcnt bookkeeping
     // conservative and the next wait would drain the prefetch as well.
     const int grp_last = ngroups - 1;
-    auto issue = [&](uint4 (&ld)[NSB][4], bf16x8 (&bh)[NT], bf16x8 (&bl)[NT], int grp_, unsigned pm) {
+    auto issue = [&](uint4 (&ld)[4], bf16x8 (&bh)[NT], bf16x8 (&bl)[NT], int grp_, unsigned pm) {
         const int grp = min(grp_, grp_last);
         const int t0 = grp << 5;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const size_t rowoff = (size_t)min(t0 + 8 * u + lrow, a.T - 1) * a.C;
-#pragma unroll
-            for (int sb = 0; sb < NSB; ++sb) {
-                const int c = min(c_begin + sb * 64 + lcol * 8, a.C - 8);           // C % 32 == 0; columns >= C never reach the output
-                ld[sb][u] = *(const uint4*)(a.in + (rowoff + c) * 2);
-            }
+            const int c = min(c_begin + lcol * 8, a.C - 8);                         // C % 32 == 0; columns >= C never reach the output
+            ld[u] = *(const uint4*)(a.in + (rowoff + c) * 2);
         }
         load_pack(bh, bl, grp, pm ? __builtin_ctz(pm) : 0);
     };
     // bhx / blx: pack fragments of the SECOND modality of a group that straddles a span boundary.  They are
     // requested (conditionally) BEFORE the unconditional prefetch of the next group goes out: the compiler's
     // conservative vmcnt for "maybe issued" loads is then still exact for everything older than the prefetch.
-    auto compute = [&](uint4 (&ld)[NSB][4], bf16x8 (&bh0)[NT], bf16x8 (&bl0)[NT], bf16x8 (&bhx)[NT], bf16x8 (&blx)[NT], int grp, unsigned pm) {
+    auto compute = [&](uint4 (&ld)[4], bf16x8 (&bh0)[NT], bf16x8 (&bl0)[NT], bf16x8 (&bhx)[NT], bf16x8 (&blx)[NT], int grp, unsigned pm) {
         const int mfirst = __builtin_ctz(pm);
         const unsigned rest = pm & (pm - 1);
         const int msecond = rest ? __builtin_ctz(rest) : -1;
         ever |= pm;
 #pragma unroll
-        for (int sb = 0; sb < NSB; ++sb) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                uint4 v = ld[sb][u];
-                if (a.drop.thr) {
-                    const unsigned trow = (unsigned)min((grp << 5) + 8 * u + lrow, a.T - 1);
-                    const KeepMask keep = drop_keep8(a.drop, ep, trow * (unsigned)(a.C >> 3) + (unsigned)((c_begin + sb * 64) >> 3) + (unsigned)lcol);
-                    bf16x8 t8 = drop_apply(*(bf16x8*)&v, keep);
-                    v = *(uint4*)&t8;
-                }
-                *(uint4*)(my + (sb * 32 + 8 * u + lrow) * PITCH + lcol * 16) = v;
+        for (int u = 0; u < 4; ++u) {
+            uint4 v = ld[u];
+            if (a.drop.thr) {
+                const unsigned trow = (unsigned)min((grp << 5) + 8 * u + lrow, a.T - 1);
+                const KeepMask keep = drop_keep8(a.drop, ep, trow * (unsigned)(a.C >> 3) + (unsigned)(c_begin >> 3) + (unsigned)lcol);
+                bf16x8 t8 = drop_apply(*(bf16x8*)&v, keep);
+                v = *(uint4*)&t8;
             }
+            *(uint4*)(my + (8 * u + lrow) * PITCH + lcol * 16) = v;
         }
         // one pass over the transposed tile per modality present (exactly one, except on span boundaries)
 #pragma unroll
@@ -135,24 +127,22 @@ __global__ void __launch_bounds__(NW * G * 64) moka_wgrad_kernel(const WgradBatc
                 load_pack(bh, bl, grp, m);                        // three modalities inside 32 tokens
             }
 #pragma unroll
-            for (int sb = 0; sb < NSB; ++sb)
+            for (int ct = 0; ct < CT; ++ct) {
+                const unsigned char* base = my + (4 * g + (i >> 2)) * PITCH + (ct * 16 + 4 * (i & 3)) * 2;
+                const bf16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_TR_PTR(base));
+                const bf16x4 a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_TR_PTR(base + 16 * PITCH));
+                const bf16x8 av = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
 #pragma unroll
-                for (int ct = 0; ct < CT; ++ct) {
-                    const unsigned char* base = my + (sb * 32 + 4 * g + (i >> 2)) * PITCH + (ct * 16 + 4 * (i & 3)) * 2;
-                    const bf16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_TR_PTR(base));
-                    const bf16x4 a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_TR_PTR(base + 16 * PITCH));
-                    const bf16x8 av = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) {
-                        acc[m][sb][ct][nt] = MFMA16(av, bh[nt], acc[m][sb][ct][nt]);
-                        acc[m][sb][ct][nt] = MFMA16(av, bl[nt], acc[m][sb][ct][nt]);
-                    }
+                for (int nt = 0; nt < NT; ++nt) {
+                    acc[m][ct][nt] = MFMA16(av, bh[nt], acc[m][ct][nt]);
+                    acc[m][ct][nt] = MFMA16(av, bl[nt], acc[m][ct][nt]);
                 }
+            }
         }
     };
 
     // ---- 2-deep pipeline over this wave's CONTIGUOUS run of groups (routing bytes two groups ahead)
-    uint4 ldA[NSB][4], ldB[NSB][4];
+    uint4 ldA[4], ldB[4];
     bf16x8 bhA[NT], blA[NT], bhB[NT], blB[NT], bhx[NT], blx[NT];
     const int per_wave = (grp_end - grp_begin + NW - 1) / NW;
     int grp = grp_begin + wave * per_wave;
@@ -207,15 +197,13 @@ __global__ void __launch_bounds__(NW * G * 64) moka_wgrad_kernel(const WgradBatc
         float* mine = own ? (float*)my : red + (size_t)wave_all * RSZ;
         // D[row = column c (4g+reg)][col = rank k (i)]
 #pragma unroll
-        for (int sb = 0; sb < NSB; ++sb)
+        for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
+            for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                    for (int reg = 0; reg < 4; ++reg)
-                        mine[OUT_CK ? (sb * 64 + ct * 16 + 4 * g + reg) * RPITCH + nt * 16 + i
-                                    : (nt * 16 + i) * RPITCH + sb * 64 + ct * 16 + 4 * g + reg] = acc[m][sb][ct][nt][reg];
+                for (int reg = 0; reg < 4; ++reg)
+                    mine[OUT_CK ? (ct * 16 + 4 * g + reg) * RPITCH + nt * 16 + i
+                                : (nt * 16 + i) * RPITCH + ct * 16 + 4 * g + reg] = acc[m][ct][nt][reg];
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         for (int e2 = tid; e2 < G * CCB * RP; e2 += NW * G * 64) {
             // consecutive threads -> consecutive addresses of the destination ([C][r] for dB, [r][C] for dA)
@@ -505,15 +493,15 @@ static bool det_prepare(WgradBatch& ab, int nz, int per_entry, int nruns, size_t
 }
 
 #define det_finish mk_det_finish
-template <int RP, int NSB, int NW, bool OUT_CK, int G>
+template <int RP, int NW, bool OUT_CK, int G>
 static void launch_wgrad_t(WgradBatch& ab, int nz, hipStream_t st) {
-    constexpr int CCB = NSB * 64;
+    constexpr int CCB = 64;
     int Cmax = 0;
     for (int z = 0; z < nz; ++z) Cmax = ab.z[z].C > Cmax ? ab.z[z].C : Cmax;
     const int nc = (Cmax + CCB - 1) / CCB;
     const int ngroups = ab.z[0].Tp / 32;
     // 4-wave blocks (wide inputs): three per CU, so that the 172 column blocks of an 11008-wide input spread evenly (55 -> 50 us)
-    const int bpc = g_tune_wgrad_bpc > 0 ? g_tune_wgrad_bpc : ((NW == 4 && G == 1) ? 3 : 1);
+    const int bpc = (NW == 4 && G == 1) ? 3 : 1;
     const int nzg = (G == 1) ? nz : 1;                  // grid z
     int nb = (bpc * num_cu() + nc * nzg - 1) / (nc * nzg);
     if (nb > (ngroups + NW - 1) / NW) nb = (ngroups + NW - 1) / NW;
@@ -521,16 +509,16 @@ static void launch_wgrad_t(WgradBatch& ab, int nz, hipStream_t st) {
     const int gpb = (ngroups + nb - 1) / nb;
     for (int z = 0; z < nz; ++z) ab.z[z].groups_per_block = gpb;
     nb = (ngroups + gpb - 1) / gpb;
-    const size_t lds = (size_t)NW * G * NSB * 32 * 160 + (size_t)NW * G * (OUT_CK ? CCB * RP : RP * (CCB + 1)) * 4 + 64;
+    const size_t lds = (size_t)NW * G * 32 * 160 + (size_t)NW * G * (OUT_CK ? CCB * RP : RP * (CCB + 1)) * 4 + 64;
     SumRunsArgs sr;
     const bool det = det_prepare(ab, nz, OUT_CK ? 1 : ab.z[0].M, nb, (size_t)Cmax * ab.z[0].r, &sr);
     if (det) {
-        ensure_lds((const void*)moka_wgrad_kernel<RP, NSB, NW, OUT_CK, G, true>, lds);
-        hipLaunchKernelGGL((moka_wgrad_kernel<RP, NSB, NW, OUT_CK, G, true>), dim3(nc, nb, nzg), dim3(NW * G * 64), lds, st, ab);
+        ensure_lds((const void*)moka_wgrad_kernel<RP, NW, OUT_CK, G, true>, lds);
+        hipLaunchKernelGGL((moka_wgrad_kernel<RP, NW, OUT_CK, G, true>), dim3(nc, nb, nzg), dim3(NW * G * 64), lds, st, ab);
         det_finish(sr, st);
     } else {
-        ensure_lds((const void*)moka_wgrad_kernel<RP, NSB, NW, OUT_CK, G, false>, lds);
-        hipLaunchKernelGGL((moka_wgrad_kernel<RP, NSB, NW, OUT_CK, G, false>), dim3(nc, nb, nzg), dim3(NW * G * 64), lds, st, ab);
+        ensure_lds((const void*)moka_wgrad_kernel<RP, NW, OUT_CK, G, false>, lds);
+        hipLaunchKernelGGL((moka_wgrad_kernel<RP, NW, OUT_CK, G, false>), dim3(nc, nb, nzg), dim3(NW * G * 64), lds, st, ab);
     }
 }
 
@@ -541,8 +529,7 @@ static void launch_wgrad_wide(WgradBatch& ab, int nz, hipStream_t st) {
     for (int z = 0; z < nz; ++z) Cmax = ab.z[z].C > Cmax ? ab.z[z].C : Cmax;
     const int nc = (Cmax + 63) / 64;
     const int ngroups = ab.z[0].Tp / 32;
-    const int target = g_tune_wgrad_bpc > 0 ? g_tune_wgrad_bpc * num_cu() : num_cu();
-    int nb = target / (nc * nz);                        // never more blocks than CUs: a second round would double the launch
+    int nb = num_cu() / (nc * nz);                      // never more blocks than CUs: a second round would double the launch
     if (nb > (ngroups + 7) / 8) nb = (ngroups + 7) / 8;
     if (nb < 1) nb = 1;
     const int gpb = (ngroups + nb - 1) / nb;
@@ -561,7 +548,7 @@ static void launch_wgrad_wide(WgradBatch& ab, int nz, hipStream_t st) {
     }
 }
 
-// OUT_CK: nz batched problems.  !OUT_CK: nz projections sharing x (one kernel when can_group()).
+// OUT_CK: nz batched problems.  !OUT_CK: nz projections sharing x (r <= 16: one kernel, wave set g of a block works on projection g).
 // zbatch (dA): the nz projections as independent problems of one launch (grid z) instead of wave sets that share a tile
 template <bool OUT_CK>
 static int launch_wgrad(WgradBatch& ab, int nz, int RP, hipStream_t st, bool zbatch = false) {
@@ -570,17 +557,16 @@ static int launch_wgrad(WgradBatch& ab, int nz, int RP, hipStream_t st, bool zba
         return check_launch("moka_wgrad_wide_kernel");
     }
     if (OUT_CK || nz == 1 || zbatch) {
-        if (RP == 16) {
-            if (g_tune_wgrad_ct == 2) launch_wgrad_t<16, 2, 8, OUT_CK, 1>(ab, nz, st);
-            else if (g_tune_wgrad_nw == 4 || (g_tune_wgrad_nw == 0 && !OUT_CK && ab.z[0].C > 8192)) launch_wgrad_t<16, 1, 4, OUT_CK, 1>(ab, nz, st);   // measured at C = 11008: 56 vs 60 us
-            else launch_wgrad_t<16, 1, 8, OUT_CK, 1>(ab, nz, st);
-        } else launch_wgrad_t<32, 1, 8, OUT_CK, 1>(ab, nz, st);
-    } else if (RP == 16) {                               // can_group()
-        if (nz == 2) launch_wgrad_t<16, 1, 4, false, 2>(ab, nz, st);
-        else launch_wgrad_t<16, 1, 4, false, 3>(ab, nz, st);
-    } else {                                             // rank pad 32: 240 registers, two waves per SIMD: three sets of two waves
-        if (nz == 2) launch_wgrad_t<32, 1, 4, false, 2>(ab, nz, st);
-        else launch_wgrad_t<32, 1, 2, false, 3>(ab, nz, st);
+        if (RP == 32) launch_wgrad_t<32, 8, OUT_CK, 1>(ab, nz, st);
+        else {
+            if constexpr (!OUT_CK) {                     // dA of a wide input: 4-wave blocks (measured at C = 11008: 56 vs 60 us); dB always takes the 8-wave form
+                if (ab.z[0].C > 8192) { launch_wgrad_t<16, 4, false, 1>(ab, nz, st); return check_launch("moka_wgrad_kernel"); }
+            }
+            launch_wgrad_t<16, 8, OUT_CK, 1>(ab, nz, st);
+        }
+    } else {                                             // RP == 16, G projections as wave sets (rank pad 32 groups arrive as a z-batch: the wave-set form measured and lost)
+        if (nz == 2) launch_wgrad_t<16, 4, false, 2>(ab, nz, st);
+        else launch_wgrad_t<16, 4, false, 3>(ab, nz, st);
     }
     return check_launch("moka_wgrad_kernel");
 }

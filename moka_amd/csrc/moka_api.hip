@@ -1,5 +1,5 @@
 // libmoka_hip.so: the C ABI of include/moka_hip.h -- argument validation, the per-call state, which kernel form serves which shape (the
-// launch RULES; the kernels and their launch helpers live in k_*.hip), the diagnostics switches.  No kernel is compiled from this file:
+// launch RULES; the kernels and their launch helpers live in k_*.hip).  No kernel is compiled from this file:
 // a rule change rebuilds in seconds.
 #include "moka_host.h"
 
@@ -9,9 +9,6 @@ thread_local DetCall t_det = {nullptr, 0};
 thread_local size_t g_det_need = 0;
 thread_local int t_company = 1;
 thread_local const unsigned* t_seed_dev = nullptr;
-#ifdef MOKA_DIAGNOSTICS
-int g_tune_dx_group = 0, g_tune_gy_form = 0, g_tune_xa_form = 0, g_tune_expand_nq = 0, g_tune_xa_ng = 0, g_tune_expand_depth = 0, g_tune_gy_ng = 0, g_tune_wgrad_nw = 0, g_tune_expand_bpc = 0, g_tune_wgrad_ct = 0, g_tune_wgrad_bpc = 0, g_tune_yx_bpc = 0, g_tune_yx_cpb = 0, g_tune_yx_dbg = 0, g_tune_g32_fwd = 0, g_tune_g32_dx = 0, g_tune_g32_da = 0, g_tune_gs_dbg = 0, g_tune_g64_da = 0, g_tune_cu_div = 0, g_tune_yx_fill = 0, g_tune_xs_wide = 0, g_tune_yx_xcd = 0;
-#endif
 
 // ---- fp32 storage launchers (one projection at a time)
 static void f32_common(F32Args& a, const uint8_t* tok_mod, int T, int C, int r, int M) {
@@ -77,47 +74,13 @@ int moka_device_check(void) {
     return MOKA_OK;
 }
 
+// Kept in the ABI (include/moka_hip.h); there is nothing left to set.
 int moka_tune(const char* key, int value) {
-    if (!key) return fail(MOKA_EINVAL, "moka_tune: null key");
-#ifdef MOKA_DIAGNOSTICS
-    if (!strcmp(key, "wgrad_nw")) g_tune_wgrad_nw = value;
-    else if (!strcmp(key, "gy_ng")) g_tune_gy_ng = value;
-    else if (!strcmp(key, "expand_depth")) g_tune_expand_depth = value;
-    else if (!strcmp(key, "xa_ng")) g_tune_xa_ng = value;
-    else if (!strcmp(key, "xa_form")) g_tune_xa_form = value;
-    else if (!strcmp(key, "dx_group")) g_tune_dx_group = value;
-    else if (!strcmp(key, "gy_form")) g_tune_gy_form = value;
-    else if (!strcmp(key, "expand_nq")) g_tune_expand_nq = value;
-    else if (!strcmp(key, "expand_bpc")) g_tune_expand_bpc = value;
-    else if (!strcmp(key, "wgrad_ct")) g_tune_wgrad_ct = value;
-    else if (!strcmp(key, "wgrad_bpc")) g_tune_wgrad_bpc = value;
-    else if (!strcmp(key, "yx_bpc")) g_tune_yx_bpc = value;
-    else if (!strcmp(key, "yx_cpb")) g_tune_yx_cpb = value;
-    else if (!strcmp(key, "yx_dbg")) g_tune_yx_dbg = value;
-    else if (!strcmp(key, "g32_fwd")) g_tune_g32_fwd = value;
-    else if (!strcmp(key, "g32_dx")) g_tune_g32_dx = value;
-    else if (!strcmp(key, "g32_da")) g_tune_g32_da = value;
-    else if (!strcmp(key, "gs_dbg")) g_tune_gs_dbg = value;
-    else if (!strcmp(key, "g64_da")) g_tune_g64_da = value;
-    else if (!strcmp(key, "cu_div")) g_tune_cu_div = value;
-    else if (!strcmp(key, "yx_fill")) g_tune_yx_fill = value;
-    else if (!strcmp(key, "xs_wide")) g_tune_xs_wide = value;
-    else if (!strcmp(key, "yx_xcd")) g_tune_yx_xcd = value;
-    else return fail(MOKA_EINVAL, "moka_tune: unknown key %s", key);
-    return MOKA_OK;
-#else
     (void)value;
-    return fail(MOKA_EINVAL, "moka_tune(%s): launch-heuristic overrides exist only in the diagnostics build (python -m moka_amd.build --diag, "
-                "MOKA_HIP_LIB=.../libmoka_hip_diag.so); the product library keeps no mutable state", key);
-#endif
+    return fail(MOKA_EINVAL, "moka_tune(%s): launch-heuristic overrides went away with the diagnostics build; the library keeps no mutable state "
+                "(compare builds with MOKA_HIP_LIB, measure marginals with bench.py --ablate)", key ? key : "(null)");
 }
-int moka_diagnostics(void) {
-#ifdef MOKA_DIAGNOSTICS
-    return 1;
-#else
-    return 0;
-#endif
-}
+int moka_diagnostics(void) { return 0; }
 int moka_rank_pad(int r) { return rank_pad(r); }
 int moka_tok_pad(int T) { return T < 0 ? MOKA_EINVAL : (T + 31) / 32 * 32; }
 
@@ -136,12 +99,9 @@ int moka_up_bwd_passes(int r, int dtype) {
 
 int moka_ksplit_group(int T, int C, int r, int G) {
     if (rank_pad(r) < 0 || C < 32 || (C % 32) != 0 || T < 1 || G < 1 || G > MOKA_MAX_GROUP) return MOKA_EINVAL;
-    return fwd_ks(T, C, r, G);
+    return fwd_ks(T, C, r);
 }
 int moka_ksplit(int T, int C, int r) { return moka_ksplit_group(T, C, r, 1); }
-
-// shared-input groups run as ONE kernel for r <= 16; wider ranks fall back to one launch per projection
-static bool can_group(int r, int G) { return G > 1 && rank_pad(r) == 16; }
 
 int moka_down_fwd_group(const void* x, const void* const* A, const uint8_t* tok_mod, float* const* part,
                         int T, int d_in, int r, int M, int G, float s_in, float dropout_p, const unsigned long long* seeds,
@@ -177,32 +137,26 @@ int moka_down_fwd_group(const void* x, const void* const* A, const uint8_t* tok_
             f32_common(a, tok_mod, T, d_in, r, M);
             a.in = (const float*)x; a.out = part[g]; a.drop = drop[g];
             for (int m = 0; m < M; ++m) { a.W[m] = (const float*)A[g * M + m]; a.s_mod[m] = s_in * drop[g].inv_keep; }
-            mk_f32_reduce(false, a, dim3(fwd_ks(T, d_in, r, G), (T + 15) / 16), fwd_kw(T, d_in, r, G), (hipStream_t)stream);
+            mk_f32_reduce(false, a, dim3(fwd_ks(T, d_in, r), (T + 15) / 16), fwd_kw(T, d_in, r), (hipStream_t)stream);
             rc = check_launch("moka_f32_reduce_kernel");
             if (rc) return rc;
         }
         return MOKA_OK;
     }
     const int RP = rank_pad(r);
-    // r <= 16: the weights of all modalities (and of all G projections) are resident per wave -> one launch for the group;
+    // ONE launch for the group at every rank.  r <= 16: the weights of all modalities (and of all G projections) are resident per wave.
     // One split-K slice per 512 columns (rank pads 32 / 64: fwd_kw).
     // rank pad 64: the chunk-walk kernel takes the whole group too (13B widths: x.A^T 11.05 -> 9.6 ms per pass: q/k/v 3 x 28 -> 70 us)
-    // rank pad 32: the same chunk-walk kernel (7B widths, r = 32: x.A^T 7.33 -> 5.88 ms per pass; "g32_fwd" 1: moka_xw_kernel, one launch per projection)
-    const bool xwm32 = RP == 32 && use_xw(32) && g_tune_g32_fwd != 1;
-    const int per_launch = (RP == 16 || (RP == 64 && use_xw(64) && g_tune_xa_form != 3) || xwm32) ? G : 1;
-    for (int g0 = 0; g0 < G; g0 += per_launch) {
-        XaArgs xa;
-        memset(&xa, 0, sizeof(xa));
-        xa.x = (const unsigned char*)x; xa.tok_mod = tok_mod; xa.T = T; xa.C = d_in; xa.r = r; xa.M = M;
-        for (int m = 0; m < M; ++m) xa.s_mod[m] = s_in * inv_keep;
-        for (int g = 0; g < per_launch; ++g) {
-            xa.part[g] = part[g0 + g]; xa.drop[g] = drop[g0 + g];
-            for (int m = 0; m < M; ++m) xa.A[g][m] = (const unsigned char*)A[(g0 + g) * M + m];
-        }
-        rc = mk_launch_down_fwd(xa, G, per_launch, RP, T, d_in, r, xwm32, (hipStream_t)stream);
-        if (rc) return rc;
+    // rank pad 32: the same chunk-walk kernel (7B widths, r = 32: x.A^T 7.33 -> 5.88 ms per pass)
+    XaArgs xa;
+    memset(&xa, 0, sizeof(xa));
+    xa.x = (const unsigned char*)x; xa.tok_mod = tok_mod; xa.T = T; xa.C = d_in; xa.r = r; xa.M = M;
+    for (int m = 0; m < M; ++m) xa.s_mod[m] = s_in * inv_keep;
+    for (int g = 0; g < G; ++g) {
+        xa.part[g] = part[g]; xa.drop[g] = drop[g];
+        for (int m = 0; m < M; ++m) xa.A[g][m] = (const unsigned char*)A[g * M + m];
     }
-    return MOKA_OK;
+    return mk_launch_down_fwd(xa, G, RP, (hipStream_t)stream);
 }
 
 int moka_down_fwd(const void* x, const void* const* A, const uint8_t* tok_mod, float* part,
@@ -412,13 +366,12 @@ int moka_up_fwd_fused_group(const float* const* part, int ks, const moka_routing
     for (int m = 0; m < rt->M; ++m) fb.s_mod[m] = s_out[m];
     fb.ks = ks; fb.B = rt->B; fb.S = rt->S; fb.T = T; fb.Lkp = rt->Lk_max > 0 ? rt->Lk_max : 1; fb.r = r;
     fb.w = w; fb.c = inv_sqrt_dk;
-    fb.dbg = g_tune_yx_dbg;
     // the column ranges of a token block on one XCD (round 5: up-projection 12.48 -> 11.99 ms per pass on 4096-token launches, step 30.90 -> 30.56 ms,
-    // three same-box pairs; "yx_xcd" 2: the plain numbering)
+    // three same-box pairs)
     // (the remap hard-codes EIGHT XCDs dealt round-robin -- the MI355X / MI350X layout, 256 CUs = 8 x 32.  The library only runs on
     //  gfx950 (moka_device_check), but a part or partition mode that exposes another CU count -- CPX: one XCD per device -- gets the plain
     //  numbering: there the remap would only shuffle workgroup ids)
-    fb.xcd = g_tune_yx_xcd != 2 && num_cu() == 256;
+    fb.xcd = num_cu() == 256;
     const int RPx = rank_pad(r);
     return mk_launch_yx(fb, G, RPx, (hipStream_t)stream);
 }
@@ -699,7 +652,6 @@ int moka_down_bwd_group(const void* const* dh_tok, const void* const* dh_kmj, co
         }
         return MOKA_OK;
     }
-    const bool fused = G == 1 || can_group(r, G);
     if (dA_acc) {
         if (!dh_kmj || !x) return fail(MOKA_EINVAL, "moka_down_bwd: dA requested without dh_kmj / x");
         WgradBatch gb;
@@ -714,22 +666,13 @@ int moka_down_bwd_group(const void* const* dh_tok, const void* const* dh_kmj, co
             }
             ga.T = T; ga.Tp = (T + 31) / 32 * 32; ga.C = d_in; ga.r = r; ga.M = M; ga.per_mod = 1; ga.drop = drop[g];
         }
-        // (rank pad 32: G sets of waves on one x tile lose to G launches -- 240 registers, one 6- or 8-wave workgroup per CU: dx + dA 14.6 -> 14.9 ms
-        //  per pass at the 7B widths; "g32_da" 2 runs them; the default is the G problems as one launch of the single kernel, grid z)
-        //  rank pad 64: the G problems as ONE launch (grid z) of the wide kernel: the sibling workgroups of an x strip run side by side, so
-        //  the repeats of the strip are served on die, and the group costs one launch start-up; "g64_da" 1: a launch per projection)
-        if (fused || (RP == 32 && G > 1 && g_tune_g32_da != 1) || (RP == 64 && G > 1 && g_tune_g64_da != 1)) {
-            rc = mk_launch_wgrad(false, gb, G, RP, (hipStream_t)stream, RP == 32 && g_tune_g32_da != 2);
-            if (rc) return rc;
-        } else {
-            for (int g = 0; g < G; ++g) {
-                WgradBatch one;
-                memset(&one, 0, sizeof(one));
-                one.z[0] = gb.z[g];
-                rc = mk_launch_wgrad(false, one, 1, RP, (hipStream_t)stream);
-                if (rc) return rc;
-            }
-        }
+        // r <= 16: the G projections as wave sets that share one x tile
+        // rank pad 32: the G problems as one launch of the single kernel, grid z (measured and lost: G sets of waves on one x tile -- 240 registers,
+        //  one 6- or 8-wave workgroup per CU: dx + dA 14.6 -> 14.9 ms per pass at the 7B widths)
+        // rank pad 64: the G problems as ONE launch (grid z) of the wide kernel: the sibling workgroups of an x strip run side by side, so
+        //  the repeats of the strip are served on die, and the group costs one launch start-up
+        rc = mk_launch_wgrad(false, gb, G, RP, (hipStream_t)stream, RP == 32);
+        if (rc) return rc;
     }
     if (dx_inout) {
         if (!dh_tok || !AT) return fail(MOKA_EINVAL, "moka_down_bwd: dx requested without dh_tok / AT");
@@ -742,17 +685,8 @@ int moka_down_bwd_group(const void* const* dh_tok, const void* const* dh_kmj, co
             for (int m = 0; m < M; ++m) a.W[m] = (const unsigned char*)AT[g] + (size_t)m * d_in * RP * 2;
             a.T = T; a.C = d_in; a.r = r; a.M = M; a.drop = drop[g];
         }
-        // rank pad 64: the group's dx terms in one pass over dx too (moka_dxg_kernel; "dx_group" 1: one pass per projection)
-        if (fused || (RP == 64 && G > 1 && g_tune_dx_group != 1) || (RP == 32 && G > 1 && g_tune_g32_dx != 1)) {
-            rc = mk_launch_expand(false, eb, G, RP, (hipStream_t)stream);
-        } else {
-            for (int g = 0; g < G && !rc; ++g) {
-                ExpandBatch one;
-                memset(&one, 0, sizeof(one));
-                one.z[0] = eb.z[g];
-                rc = mk_launch_expand(false, one, 1, RP, (hipStream_t)stream);
-            }
-        }
+        // the group's dx terms in one pass over dx at every rank
+        rc = mk_launch_expand(false, eb, G, RP, (hipStream_t)stream);
     }
     return rc;
 }

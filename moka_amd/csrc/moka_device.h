@@ -37,7 +37,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // Guard in front of LDS / global stores that read an MFMA accumulator directly.  History: round 1 saw intermittent NaN rows (ragged
 // widths) when the SECOND K step of the xa / gy kernels sat behind a wave-uniform branch -- on the skipping path the store followed
 // the first MFMA after only a branch -- and fixed it twice over: the second step became branch-free (operand zeroed instead) and this
-// guard was added.  Round 2 looked at the ISA of the branch-free code (hipcc -save-temps, moka_xa_kernel<16,1,4>): on every path the
+// guard was added.  Round 2 looked at the ISA of the branch-free code (hipcc -save-temps, moka_xa_kernel<1,4>): on every path the
 // compiler's own spacing between the last v_mfma and the ds_write2_b32 that reads its result is 8-12 wait states (fall-through:
 // s_or / s_xor / 4 v_mov / s_nop 1; via the modality branches 11-12), at or above the 7 the hazard table asks for a 4-pass XDL op,
 // and a build WITHOUT the guard passed 13 x 23 runs of the group / ragged / fuzz / 70B-width tests.  So the branch-free rewrite was
@@ -436,7 +436,8 @@ struct YxBatch {
     float s_mod[4];                 // s_out per modality
     int ks, B, S, T, Tp, Lkp, r;
     float w, c;
-    int dbg;                        // diagnostics build only (timing ablations, wrong results): 1 = no interaction, 2 = no slice sums either
+    int dbg;                        // always 0 (memset by the entry point).  A timing ablation of the former diagnostics build: 1 = no interaction, 2 = no slice sums either.  Kept
+                                    // because taking the field and its two never-taken tests out of moka_yx_kernel cost the benchmarked step 3 % (29.4 -> 30.3 ms, same box, twice)
     int xcd;                        // 1: the column ranges of a token block on ONE XCD (workgroup ids go round the 8 XCDs): the slices they all sum are fetched into one L2
 };
 
@@ -473,7 +474,7 @@ struct GyBatch {
     GyArgs z[MOKA_MAX_GROUP];
     int xend[MOKA_MAX_GROUP];      // blockIdx.x < xend[z] belongs to problem z: its column blocks, plus ONE block per token run that zeroes
     int ncb_max;                   // the slices a narrower member leaves unwritten (the group's consumers read ncb_max slices of everyone)
-    int dbg;                       // diagnostics build only (timing ablation, wrong results): 1 = the dB sums are not sent to memory
+    int dbg;                       // always 0 (memset by the entry point); a timing ablation of the former diagnostics build (1 = the dB sums are not sent to memory), kept with YxBatch::dbg
 };
 
 struct XaArgs {

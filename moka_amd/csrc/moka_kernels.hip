@@ -39,7 +39,7 @@
 // tools/kernel_resources.sh compiles it for the register / LDS table.  The product build (moka_amd/build.py) compiles the translation units
 // separately and in parallel:
 //   moka_device.h   device idioms, operand-pack layouts, the dropout mask, the kernels' argument structs
-//   moka_host.h     per-call state, error reporting, diagnostics overrides, shape rules, what the families export
+//   moka_host.h     per-call state, error reporting, shape rules, what the families export
 //   k_cross.hip     the rank-r interaction (fwd / bwd / key rows) + weight shadows
 //   k_expand.hip    y += hp B^T (incl. the fused interaction + up-projection) and dx += dh A_m
 //   k_wgrad.hip     dA_m / dB

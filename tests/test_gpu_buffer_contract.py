@@ -3,8 +3,8 @@ in a guard-banded arena (tests/arena.py), against the fp64 oracle.  The routing 
 exception: they stay in the routing object's own allocations (their padding past T is part of the contract) and are checked
 unchanged after every call.
 
-tests/kernel_forms.py sorts every kernel instance of the library into the forms these rows reach and the diagnostics-only ones
-(tests/test_kernel_forms_host.py keeps it in step with the built library); that the rows reach every PRODUCT instance is shown by a
+tests/kernel_forms.py lists every kernel instance of the library (tests/test_kernel_forms_host.py keeps it in step with the built
+library); that the rows reach every one of them is shown by a
 kernel trace of this file:  rocprofv3 --kernel-trace --stats -- python -m pytest tests/test_gpu_buffer_contract.py -m gpu
 
 One row per kernel form: a shape with tails (T % 16, T % 32, T % 128 != 0 where the form allows; widths with C % 128 in {32, 96},
@@ -461,25 +461,25 @@ def _pipeline(cfg, shift):
 # comments).  Shapes: T % 16 != 0 unless the form needs whole 16-token tiles, C % 128 in {32, 96}, C % 512 != 0.
 ROWS = [
     # -- down-projection, rank pad 16
-    # k_reduce.hip:1260 (T % 16 == 0) -> moka_xs_kernel<G>; gs<16, dB> (k_reduce.hip:1101); fused yx<16> (moka_api.hip:342: C <= 6144);
-    #    moka_expand_kernel<16, 4, false, 1> dx; moka_wgrad_kernel RP 16, C <= 8192
+    # mk_launch_down_fwd (T % 16 == 0) -> moka_xs_kernel<G>; gs<16, dB> (launch_gy); fused yx<16> (moka_up_fwd_fused_pays: C <= 6144);
+    #    moka_expand_kernel<16, 4, false, 1, false> dx; moka_wgrad_kernel RP 16, C <= 8192
     dict(id="xs1_yx16_r16", variant="avt", r=16, B=2, S=520, d_in=1376, d_outs=(1120,), p=0.1),
-    # k_reduce.hip:1261 moka_xs_kernel<2>; moka_expand_kernel<16, 2, false, 2> dx; wgrad G = 2; fused group (moka_api.hip:342: G > 1)
+    # moka_xs_kernel<2>; moka_expand_kernel<16, 2, false, 2, false> dx; wgrad G = 2; fused group (moka_up_fwd_fused_pays: G > 1)
     dict(id="xs2_group_r16", variant="vt", r=12, B=2, S=272, d_in=1120, d_outs=(1376, 1376)),
-    # k_reduce.hip:1262 moka_xs_kernel<3>; wgrad G = 3; up_fwd two-launch, unequal widths (fused_pays: widths differ)
+    # moka_xs_kernel<3>; wgrad G = 3; up_fwd two-launch, unequal widths (fused_pays: widths differ)
     dict(id="xs3_unequal_r16", variant="avt", r=16, B=1, S=1040, d_in=1376, d_outs=(1120, 352, 160), det=True),
-    # k_reduce.hip:1263 / :1220 moka_xa_kernel<16, 1, 2> (G == 1, C > 8192, T % 16 != 0); wgrad RP 16 with C > 8192 (4-wave form)
+    # launch_xa: moka_xa_kernel<1, 2> (G == 1, C > 8192, T % 16 != 0); wgrad RP 16 with C > 8192 (4-wave form)
     dict(id="xa1_wide_r16", variant="avt", r=16, B=1, S=1001, d_in=8224, d_outs=(1120,), p=0.1),
-    # moka_xa_kernel<16, 2, 4>
+    # moka_xa_kernel<2, 4>
     dict(id="xa2_r16", variant="vt", r=16, B=3, S=333, d_in=1376, d_outs=(352, 1120), p=0.1),
-    # moka_xa_kernel<16, 3, 8>; moka_yt_kernel<16> (batched equal widths, two-launch forced); cross_bwd on long key lists
+    # moka_xa_kernel<3, 8>; moka_yt_kernel<16> (batched equal widths, two-launch forced); cross_bwd on long key lists
     dict(id="xa3_yt16_r16", variant="avt", r=16, B=2, S=1037, d_in=1376, d_outs=(1120, 1120, 1120), fused=False),
-    # single projection C > 6144: cross_fwd + moka_expand_kernel<16, ...> (moka_api.hip:342)
+    # single projection C > 6144: cross_fwd + moka_expand_kernel<16, ...> (moka_up_fwd_fused_pays)
     dict(id="expand16_single_wide", variant="avt", r=16, B=1, S=999, d_in=1120, d_outs=(6240,)),
-    # k_reduce.hip:1101 moka_gy_kernel<16> (nz > 1, Cmax > 8192, T > 4096): gate + up 2 x 11008 at 4130 tokens, dropout
+    # launch_gy: moka_gy_kernel (rank pad 16, nz > 1, Cmax > 8192, T > 4096): gate + up 2 x 11008 at 4130 tokens, dropout
     dict(id="gy16_gate_up", variant="avt", r=16, B=2, S=2065, d_in=1376, d_outs=(11008, 11008), p=0.1, layouts=None),
     # -- rank pad 32
-    # moka_xwm_kernel<32, false, 1>; gs<32, dB>; fused yx<32>; moka_expand_kernel<32, 4, false, 1, 2, true> dx; wgrad RP 32
+    # moka_xwm_kernel<32, false, 1>; gs<32, dB>; fused yx<32>; moka_expand_kernel<32, 4, false, 1, true> dx; wgrad RP 32
     dict(id="xwm32_g1", variant="avt", r=24, B=1, S=1001, d_in=1376, d_outs=(1120,), p=0.1),
     # moka_xwm_kernel<32, false, 2>; moka_dxgt_kernel<32, 2>; yt<32> (two-launch, equal widths)
     dict(id="xwm32_g2_yt32", variant="vt", r=32, B=2, S=333, d_in=1376, d_outs=(1120, 1120), fused=False),
@@ -498,25 +498,25 @@ ROWS = [
 
 
     # -- forms the rows above miss (moka_hip.h: every output may be requested alone; the deterministic mode at every rank pad)
-    # k_reduce.hip:1144 NG = 16: 44 active 512-column blocks x 256 token groups x 1/16 >= 2 x 256 CUs -- gate + up at 8190 tokens, the e2e shape
-    #    -> moka_gy_kernel<16, true, 16, false, 2>; with det_ws moka_gy_kernel<16, true, 16, true, 2>
+    # launch_gy NG = 16: 44 active 512-column blocks x 256 token groups x 1/16 >= 2 x 256 CUs -- gate + up at 8190 tokens, the e2e shape
+    #    -> moka_gy_kernel<true, 16, false>; with det_ws moka_gy_kernel<true, 16, true>
     dict(id="gy16_gate_up_8k", variant="avt", r=16, B=2, S=4095, d_in=160, d_outs=(11008, 11008), shifts=(0,)),
     dict(id="gy16_gate_up_8k_det", variant="avt", r=16, B=2, S=4095, d_in=160, d_outs=(11008, 11008), det=True, p=0.1, shifts=(0,)),
-    # k_reduce.hip:1144 NG = 8 with det_ws -> moka_gy_kernel<16, true, 8, true, 2>
+    # launch_gy NG = 8 with det_ws -> moka_gy_kernel<true, 8, true>
     dict(id="gy16_gate_up_det", variant="avt", r=16, B=2, S=2065, d_in=160, d_outs=(11008, 11008), det=True, shifts=(0,)),
-    # g alone (k_reduce.hip:1139 ng = 4 without dB) -> moka_gy_kernel<16, false, 4, false, 2>; dB alone through moka_up_bwd_db_batch with det_ws
-    #    (moka_api.hip:565: one moka_up_bwd per problem) -> moka_wgrad_kernel<16, 1, 8, true, 1, true>; dA det of a pair -> moka_wgrad_kernel<16, 1, 4, false, 2, true>
+    # g alone (launch_gy: 4 groups without dB) -> moka_gy_kernel<false, 4, false>; dB alone through moka_up_bwd_db_batch with det_ws
+    #    (one moka_up_bwd per problem) -> moka_wgrad_kernel<16, 8, true, 1, true>; dA det of a pair -> moka_wgrad_kernel<16, 4, false, 2, true>
     dict(id="gy16_gate_up_det_split", variant="avt", r=16, B=2, S=2065, d_in=160, d_outs=(11008, 11008), det=True, split_bwd=True, db_batch=True,
          shifts=(0,)),
-    # rank pad 16, g and dB in separate calls: moka_gs_kernel<16, false, false>; moka_wgrad_kernel<16, 1, 8, true, 1, false> (k_wgrad.hip:576)
+    # rank pad 16, g and dB in separate calls: moka_gs_kernel<16, false, false>; moka_wgrad_kernel<16, 8, true, 1, false> (launch_wgrad)
     dict(id="split_r16", variant="avt", r=16, B=1, S=1001, d_in=1376, d_outs=(1120,), split_bwd=True),
-    # det dA of a wide input (k_wgrad.hip:575, C > 8192) -> moka_wgrad_kernel<16, 1, 4, false, 1, true>
+    # det dA of a wide input (launch_wgrad, C > 8192) -> moka_wgrad_kernel<16, 4, false, 1, true>
     dict(id="det_r16_wide", variant="avt", r=16, B=1, S=333, d_in=8224, d_outs=(160,), det=True),
-    # rank pad 32 det: moka_gs_kernel<32, true, true>, moka_wgrad_kernel<32, 1, 8, false, 1, true>
+    # rank pad 32 det: moka_gs_kernel<32, true, true>, moka_wgrad_kernel<32, 8, false, 1, true>
     dict(id="det_r32", variant="avt", r=32, B=1, S=1001, d_in=1376, d_outs=(1120,), det=True, p=0.1),
-    # rank pad 32, g and dB in separate calls: moka_gs_kernel<32, false, false>; moka_wgrad_kernel<32, 1, 8, true, 1, false>
+    # rank pad 32, g and dB in separate calls: moka_gs_kernel<32, false, false>; moka_wgrad_kernel<32, 8, true, 1, false>
     dict(id="split_r32", variant="vt", r=24, B=2, S=333, d_in=1376, d_outs=(1120,), split_bwd=True),
-    # ... dB through moka_up_bwd_db_batch with det_ws -> moka_wgrad_kernel<32, 1, 8, true, 1, true>
+    # ... dB through moka_up_bwd_db_batch with det_ws -> moka_wgrad_kernel<32, 8, true, 1, true>
     dict(id="split_r32_det", variant="avt", r=32, B=1, S=1001, d_in=1376, d_outs=(1120, 352), split_bwd=True, db_batch=True, det=True),
     # moka_up_fwd_fused at rank pad 64 (valid; moka_up_fwd_fused_pays advises against it) -> moka_yx_kernel<64>
     dict(id="yx64_fused", variant="avt", r=64, B=1, S=1001, d_in=1376, d_outs=(1120,), fused=True),

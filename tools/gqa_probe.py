@@ -1,15 +1,13 @@
 """Design probe: the batched y-expand (moka_up_fwd_group) and gy (moka_up_bwd_group) launches for members of different width
-(grouped-query k / v beside q: d_out 8192 / 1024 / 1024) against the same shapes launched alone, per expand_bpc setting.
-Run on the GPU box from the repo root."""
-import os as _os
-_os.environ.setdefault("MOKA_HIP_LIB", _os.path.join(_os.path.dirname(_os.path.dirname(_os.path.abspath(__file__))), "moka_amd", "libmoka_hip_diag.so"))   # moka_tune: diagnostics build only
+(grouped-query k / v beside q: d_out 8192 / 1024 / 1024) against the same shapes launched alone.
+Run on the GPU box from the repo root (MOKA_HIP_LIB: the library to time; default: the in-tree build)."""
 import math, os, sys, torch
 sys.path.insert(0, os.getcwd())
 import bench
 from moka_amd import _lib
 from moka_amd import functional as F
 from moka_amd.routing import MokaRouting
-lib=_lib.load(); dev=torch.device("cuda:0")
+_lib.load(); dev=torch.device("cuda:0")
 B,S,r,M=4,2048,16,3; T=B*S
 tok,q=bench.synthetic_layout(S)
 masks=[(tok==m).to(torch.int32).reshape(1,S,1).repeat(B,1,1).to(dev) for m in range(3)]
@@ -38,10 +36,6 @@ def case(d_outs):
     t_gy=timeit(lambda i: F.up_bwd_group(gys[i%NB], kmj, BwT, rt, r, [1.0]*M, dB))
     mb=sum(d_outs)*T*2/1e6
     return t_up, t_gy, mb
-for tune in ("", "expand_bpc=2", "expand_bpc=4", "expand_bpc=16"):
-    if tune:
-        k,v=tune.split("="); lib.moka_tune(k.encode(), int(v))
-    for d_outs in ((8192,),(8192,1024,1024),(1024,1024),(1024,),(8192,8192,8192)):
-        tu,tg,mb=case(d_outs)
-        print(f"{tune or 'default':14s} {str(d_outs):22s} y-expand {tu:7.1f} us ({2*mb/tu/1e0*1e-0/1e3:5.2f} TB/s rmw)   gy {tg:7.1f} us ({mb/tg/1e3:5.2f} TB/s)")
-    lib.moka_tune(b"expand_bpc", 0)
+for d_outs in ((8192,),(8192,1024,1024),(1024,1024),(1024,),(8192,8192,8192)):
+    tu,tg,mb=case(d_outs)
+    print(f"{str(d_outs):22s} y-expand {tu:7.1f} us ({2*mb/tu/1e3:5.2f} TB/s rmw)   gy {tg:7.1f} us ({mb/tg/1e3:5.2f} TB/s)")

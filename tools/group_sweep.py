@@ -1,8 +1,6 @@
-import os as _os
-_os.environ.setdefault("MOKA_HIP_LIB", _os.path.join(_os.path.dirname(_os.path.dirname(_os.path.abspath(__file__))), "moka_amd", "libmoka_hip_diag.so"))   # moka_tune: diagnostics build only
 #!/usr/bin/env python3
 """Time the grouped C entry points (q/k/v: G = 3 at 4096 -> 4096; gate/up: G = 2 at 4096 -> 11008) at the
-bench shape, each half separately.  Run on the GPU box; prints a table.  Env: B (sequences), DROP."""
+bench shape, each half separately.  Run on the GPU box; prints a table.  Env: B (sequences), DROP, ONLY, MOKA_HIP_LIB (default: the in-tree build)."""
 import math
 import os
 import sys
@@ -18,7 +16,7 @@ from moka_amd.routing import MokaRouting  # noqa: E402
 
 
 def main():
-    lib = _lib.load()
+    _lib.load()
     dev = torch.device("cuda:0")
     B, S, r, M = int(os.environ.get("B", 4)), 2048, 16, 3
     DROP = float(os.environ.get("DROP", 0.0))
@@ -71,20 +69,12 @@ def main():
             "down_bwd(dA only)": (lambda i: F.down_bwd_group_(bsts, xs[i % NBUF], None, rt, r, dA, None, DROP, seeds), E * T * d_in * G),
             "down_bwd(dx only)": (lambda i: F.down_bwd_group_(bsts, xs[i % NBUF], [s.AT for s in sts], rt, r, None, dxs[i % NBUF], DROP, seeds), 2 * E * T * d_in * G),
         }
-        sweeps = {"up_fwd": [("expand_bpc", v) for v in (2, 4, 8)], "down_bwd(dx only)": [("expand_depth", 2)] + [("expand_bpc", v) for v in (2, 4, 8)],
-                  "down_bwd(dA only)": [("wgrad_bpc", v) for v in (1, 2)], "down_fwd": [("xa_ng", v) for v in (2, 4, 8)],
-                  "up_bwd(g+dB)": [("gy_ng", v) for v in (4, 8, 16)], "up_bwd(g only)": [("gy_ng", v) for v in (4, 8, 16)]}
         print(f"\n=== G={G}: {d_in} -> {'/'.join(map(str, d_outs))}  (T={T}, dropout {DROP}) ===")
         for name, (fn, nb) in calls.items():
             if only and only not in name:
                 continue
             t = timeit(fn)
-            print(f"{name:20s} default            {t:8.1f} us  {nb / (t * 1e-6) / 1e9:7.0f} GB/s algorithmic (per-projection bytes)")
-            for key, val in sweeps.get(name, []):
-                lib.moka_tune(key.encode(), val)
-                t = timeit(fn)
-                lib.moka_tune(key.encode(), 0)
-                print(f"{'':20s} {key:12s}={val:<4d} {t:8.1f} us  {nb / (t * 1e-6) / 1e9:7.0f} GB/s")
+            print(f"{name:20s} {t:8.1f} us  {nb / (t * 1e-6) / 1e9:7.0f} GB/s algorithmic (per-projection bytes)")
         del xs, dxs, ys
         torch.cuda.empty_cache()
 

@@ -4,7 +4,6 @@
 // when the first / last wave of a launch starts relative to the end of its predecessor (boundary + ramp), how long the waves
 // live, how long the tail is.  Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -munsafe-fp-atomics -I include -I moka_amd/csrc tools/microbench/passlab.hip -o passlab
 #define MOKA_TRACE
-#define MOKA_DIAGNOSTICS
 #include "../../moka_amd/csrc/moka_kernels.hip"
 #include "passlab_cand.h"
 #include "passlab_xa2.h"
@@ -153,30 +152,30 @@ static float DROP = 0.05f;
 // the sequences: a read-modify-write launch in front (its dirty lines are what the next launch starts behind), then the pass under test
 static void rmw_front(int set, int C) { MK(moka_up_fwd(L.pack_tok, L.Bw, L.tok_mod, L.y[set], L.T, L.r, C, MOKA_BF16, 0)); }
 static int XA2_NG = 0, XA2_DP = 0;                        // != 0: the xa2 candidate instead of the library's kernel
-static int XS_NS = 0, XS_TPB = 0;                          // != 0: the xs candidate (LDS-DMA ring)
+static int XS_TPB = 0;                                     // != 0: the xs launcher of this file (LDS-DMA ring) with that many tiles per workgroup
 static void seq_xa(int set, int C) {
     rmw_front(set, 4096);
     const void* Ap[3] = {L.A[0], L.A[1], L.A[2]};
-    if (XS_NS) { float* pp[1] = {L.part}; lab_down_fwd_xs(L.x[set], Ap, L.tok_mod, pp, L.T, C, L.r, L.M, 1, 1.f, DROP, &SEED, XS_NS, XS_TPB); return; }
+    if (XS_TPB) { float* pp[1] = {L.part}; lab_down_fwd_xs(L.x[set], Ap, L.tok_mod, pp, L.T, C, L.r, L.M, 1, 1.f, DROP, &SEED, XS_TPB); return; }
     if (XA2_NG) { float* pp[1] = {L.part}; lab_down_fwd_xa2(L.x[set], Ap, L.tok_mod, pp, L.T, C, L.r, L.M, 1, 1.f, DROP, &SEED, XA2_NG, XA2_DP); return; }
-    MK(moka_down_fwd(L.x[set], Ap, L.tok_mod, L.part, L.T, C, L.r, L.M, 1.f, DROP, SEED, MOKA_BF16, 0));
+    MK(moka_down_fwd(L.x[set], Ap, L.tok_mod, L.part, L.T, C, L.r, L.M, 1.f, DROP, SEED, MOKA_BF16, nullptr, 0));
 }
 static void seq_xa3(int set, int C) {
     rmw_front(set, 4096);
     const void* Ap[9] = {L.A[0], L.A[1], L.A[2], L.A[0], L.A[1], L.A[2], L.A[0], L.A[1], L.A[2]};
     float* pp[3] = {L.part, L.part + (size_t)8 * L.T * 16, L.part + (size_t)16 * L.T * 16};
     const unsigned long long seeds[3] = {1, 2, 3};
-    if (XS_NS) { lab_down_fwd_xs(L.x[set], Ap, L.tok_mod, pp, L.T, C, L.r, L.M, 3, 1.f, DROP, DROP > 0 ? seeds : nullptr, XS_NS, XS_TPB); return; }
+    if (XS_TPB) { lab_down_fwd_xs(L.x[set], Ap, L.tok_mod, pp, L.T, C, L.r, L.M, 3, 1.f, DROP, DROP > 0 ? seeds : nullptr, XS_TPB); return; }
     if (XA2_NG) { lab_down_fwd_xa2(L.x[set], Ap, L.tok_mod, pp, L.T, C, L.r, L.M, 3, 1.f, DROP, DROP > 0 ? seeds : nullptr, XA2_NG, XA2_DP); return; }
-    MK(moka_down_fwd_group(L.x[set], Ap, L.tok_mod, pp, L.T, C, L.r, L.M, 3, 1.f, DROP, DROP > 0 ? seeds : nullptr, MOKA_BF16, 0));
+    MK(moka_down_fwd_group(L.x[set], Ap, L.tok_mod, pp, L.T, C, L.r, L.M, 3, 1.f, DROP, DROP > 0 ? seeds : nullptr, MOKA_BF16, nullptr, 0));
 }
 static void seq_xa2g(int set, int C) {
     rmw_front(set, 4096);
     const void* Ap[6] = {L.A[0], L.A[1], L.A[2], L.A[0], L.A[1], L.A[2]};
     float* pp[2] = {L.part, L.part + (size_t)8 * L.T * 16};
     const unsigned long long seeds[2] = {1, 2};
-    if (XS_NS) { lab_down_fwd_xs(L.x[set], Ap, L.tok_mod, pp, L.T, C, L.r, L.M, 2, 1.f, DROP, DROP > 0 ? seeds : nullptr, XS_NS, XS_TPB); return; }
-    MK(moka_down_fwd_group(L.x[set], Ap, L.tok_mod, pp, L.T, C, L.r, L.M, 2, 1.f, DROP, DROP > 0 ? seeds : nullptr, MOKA_BF16, 0));
+    if (XS_TPB) { lab_down_fwd_xs(L.x[set], Ap, L.tok_mod, pp, L.T, C, L.r, L.M, 2, 1.f, DROP, DROP > 0 ? seeds : nullptr, XS_TPB); return; }
+    MK(moka_down_fwd_group(L.x[set], Ap, L.tok_mod, pp, L.T, C, L.r, L.M, 2, 1.f, DROP, DROP > 0 ? seeds : nullptr, MOKA_BF16, nullptr, 0));
 }
 static void seq_gy(int set, int C) {
     rmw_front(set, 4096);
@@ -268,79 +267,43 @@ int main(int argc, char** argv) {
             out.resize((size_t)(G == 3 ? 24 : (C + 511) / 512) * L.T * 16);
             CK(hipMemcpy(out.data(), L.part, out.size() * 4, hipMemcpyDeviceToHost));
         };
-        struct Cfg { int ns, tpb; };
         for (int C : {4096, 11008}) {
             std::vector<float> ref, got;
             CK(hipMemset(L.part, 0xff, (size_t)32 * L.T * 16 * 4));
-            XS_NS = 0; seq_xa(0, C); snapshot(C, 1, ref);
+            XS_TPB = 0; seq_xa(0, C); snapshot(C, 1, ref);
             run("front + down_fwd (library)", seq_xa, C);
-            for (Cfg c : {Cfg{2, 4}, Cfg{2, 8}, Cfg{3, 4}, Cfg{3, 8}, Cfg{4, 8}}) {
+            for (int tpb : {4, 8, 16}) {
                 CK(hipMemset(L.part, 0xff, (size_t)32 * L.T * 16 * 4));
-                XS_NS = c.ns; XS_TPB = c.tpb;
+                XS_TPB = tpb;
                 seq_xa(0, C); snapshot(C, 1, got);
                 size_t bad = 0; for (size_t k = 0; k < ref.size(); ++k) if (memcmp(&ref[k], &got[k], 4)) ++bad;
-                char t[128]; snprintf(t, sizeof(t), "front + down_fwd xs<ring %d, %d tiles per block> (mismatching words: %zu)", c.ns, c.tpb, bad);
+                char t[128]; snprintf(t, sizeof(t), "front + down_fwd xs<%d tiles per block> (mismatching words: %zu)", tpb, bad);
                 run(t, seq_xa, C);
             }
-            XS_NS = 0;
+            XS_TPB = 0;
         }
         {
             std::vector<float> ref, got;
             CK(hipMemset(L.part, 0xff, (size_t)32 * L.T * 16 * 4));
-            XS_NS = 0; seq_xa3(0, 4096); snapshot(4096, 3, ref);
+            XS_TPB = 0; seq_xa3(0, 4096); snapshot(4096, 3, ref);
             run("front + down_fwd_group[q+k+v] (library)", seq_xa3, 4096);
-            for (Cfg c : {Cfg{2, 8}, Cfg{2, 16}, Cfg{3, 8}, Cfg{3, 16}}) {
+            for (int tpb : {8, 16}) {
                 CK(hipMemset(L.part, 0xff, (size_t)32 * L.T * 16 * 4));
-                XS_NS = c.ns; XS_TPB = c.tpb;
+                XS_TPB = tpb;
                 seq_xa3(0, 4096); snapshot(4096, 3, got);
                 size_t bad = 0; for (size_t k = 0; k < ref.size(); ++k) if (memcmp(&ref[k], &got[k], 4)) ++bad;
-                char t[128]; snprintf(t, sizeof(t), "front + down_fwd_group[q+k+v] xs<ring %d, %d tiles per block> (mismatching words: %zu)", c.ns, c.tpb, bad);
+                char t[128]; snprintf(t, sizeof(t), "front + down_fwd_group[q+k+v] xs<%d tiles per block> (mismatching words: %zu)", tpb, bad);
                 run(t, seq_xa3, 4096);
             }
-            XS_NS = 0;
+            XS_TPB = 0;
             run("front + down_fwd_group[gate+up] (library)", seq_xa2g, 4096);
-            for (Cfg c : {Cfg{2, 8}, Cfg{3, 8}, Cfg{3, 16}}) {
-                XS_NS = c.ns; XS_TPB = c.tpb;
-                char t[128]; snprintf(t, sizeof(t), "front + down_fwd_group[gate+up] xs<ring %d, %d tiles per block>", c.ns, c.tpb);
+            for (int tpb : {8, 16}) {
+                XS_TPB = tpb;
+                char t[128]; snprintf(t, sizeof(t), "front + down_fwd_group[gate+up] xs<%d tiles per block>", tpb);
                 run(t, seq_xa2g, 4096);
             }
-            XS_NS = 0;
+            XS_TPB = 0;
         }
-    }
-    if (what == "gs") {
-        // LDS-DMA form of the gy pass against the first form: g_part / dB within fp32 summation-order noise, then the timelines
-        auto snap = [&](int C, std::vector<float>& gp, std::vector<float>& db) {
-            CK(hipDeviceSynchronize());
-            gp.resize((size_t)((C + 511) / 512) * L.T * 16); db.resize((size_t)C * 16);
-            CK(hipMemcpy(gp.data(), L.part, gp.size() * 4, hipMemcpyDeviceToHost));
-            CK(hipMemcpy(db.data(), L.dB, db.size() * 4, hipMemcpyDeviceToHost));
-        };
-        auto relerr = [](const std::vector<float>& a, const std::vector<float>& b) { double d = 0, n = 0; for (size_t k = 0; k < a.size(); ++k) { d += (double)(a[k] - b[k]) * (a[k] - b[k]); n += (double)b[k] * b[k]; } return sqrt(d / (n > 0 ? n : 1)); };
-        for (int C : {4096, 11008}) {
-            std::vector<float> g0, d0, g1, d1;
-            moka_tune("gy_form", 1); moka_tune("gy_ng", 0);
-            CK(hipMemset(L.dB, 0, 16 * L.cmax * 4)); CK(hipMemset(L.part, 0, (size_t)32 * L.T * 16 * 4));
-            seq_gy(0, C); snap(C, g0, d0);
-            run("front + up_bwd (first form)", seq_gy, C);
-            for (int ng : {4, 8, 16}) {
-                moka_tune("gy_form", 0); moka_tune("gy_ng", ng);
-                CK(hipMemset(L.dB, 0, 16 * L.cmax * 4)); CK(hipMemset(L.part, 0, (size_t)32 * L.T * 16 * 4));
-                seq_gy(0, C); snap(C, g1, d1);
-                char t[160]; snprintf(t, sizeof(t), "front + up_bwd gs<%d groups per workgroup> (rel. diff g_part %.2e, dB %.2e)", ng, relerr(g1, g0), relerr(d1, d0));
-                run(t, seq_gy, C);
-            }
-        }
-        moka_tune("gy_form", 0); moka_tune("gy_ng", 0);
-    }
-    if (what == "front") {
-        struct Cf { int depth, bpc; };
-        for (Cf c : {Cf{0, 0}, Cf{3, 0}, Cf{3, 1}, Cf{0, 4}})
-            for (int C : {4096, 11008}) {
-                moka_tune("expand_depth", c.depth); moka_tune("expand_bpc", c.bpc);
-                char t[128]; snprintf(t, sizeof(t), "front only (up_fwd), depth=%d bpc=%d", c.depth, c.bpc);
-                run(t, [](int s, int c) { rmw_front(s, c); }, C);
-            }
-        moka_tune("expand_depth", 0); moka_tune("expand_bpc", 0);
     }
     if (what == "abl") {
         XA2_NG = 4; XA2_DP = 2;

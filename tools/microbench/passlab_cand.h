@@ -3,7 +3,7 @@
 #include <functional>
 #define NFAM 8
 
-// ---- cand0: the x stream of moka_xa_kernel<16,1,NG> alone (same block shape, same loads, two groups in flight, no weights,
+// ---- cand0: the x stream of moka_xa_kernel<1,NG> alone (same block shape, same loads, two groups in flight, no weights,
 //      no MFMA, no LDS, no stores): what the access pattern itself costs behind a read-modify-write launch
 template <int NG>
 __global__ void __launch_bounds__(512) cand_read_frag(const unsigned char* x, int T, int C, unsigned* out) {

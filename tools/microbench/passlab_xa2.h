@@ -15,6 +15,7 @@
 // ------------------------------------------------------------------------------------------
 template <int RP, int G, int NG, int DEPTH, int ABL = 0>
 __global__ void __launch_bounds__(512) moka_xa2_kernel(const XaArgs a) {
+    const uint2 ep = drop_epoch(a.drop[0]);
     constexpr int RING = DEPTH + 1;                          // one buffer more than groups in flight: the re-issue goes out BEFORE the compute
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int NT = RP / 16, NW = 8;
@@ -95,7 +96,7 @@ __global__ void __launch_bounds__(512) moka_xa2_kernel(const XaArgs a) {
                         xg[kk] = Fd[st][kk];
                         if (a.drop[gi].thr) {
                             const unsigned trow = (unsigned)min((grp << 5) + 16 * st + i, a.T - 1);
-                            xg[kk] = drop_apply(xg[kk], drop_keep8(a.drop[gi], trow * (unsigned)(a.C >> 3) + (unsigned)((c0 + 32 * kk) >> 3) + (unsigned)g));
+                            xg[kk] = drop_apply(xg[kk], drop_keep8(a.drop[gi], ep, trow * (unsigned)(a.C >> 3) + (unsigned)((c0 + 32 * kk) >> 3) + (unsigned)g));
                         }
                     }
 #pragma unroll

@@ -1,9 +1,7 @@
-import os as _os
-_os.environ.setdefault("MOKA_HIP_LIB", _os.path.join(_os.path.dirname(_os.path.dirname(_os.path.abspath(__file__))), "moka_amd", "libmoka_hip_diag.so"))   # moka_tune: diagnostics build only
 #!/usr/bin/env python3
-"""Time every C entry point at the bench shape (T = 8192, Llama-2-7B widths, r = 16, M = 3) under
-different diagnostic tuning settings (moka_tune).  Run on the GPU box; prints a table.
-env: B, S, R, DROP, WIDTHS="5120x5120,5120x13824,13824x5120", ONLY=<entry point substring>, SWEEP=0 (defaults only), MOKA_HIP_LIB=<library to time>."""
+"""Time every C entry point in isolation at the bench shape (T = 8192, Llama-2-7B widths, r = 16, M = 3).  Run on the GPU box; prints a table.
+env: B, S, R, DROP, WIDTHS="5120x5120,5120x13824,13824x5120", ONLY=<entry point substring>, MOKA_HIP_LIB=<library to time> (default: the in-tree build;
+two builds are compared by running the script once per library)."""
 import math
 import os
 import sys
@@ -110,27 +108,13 @@ def main():
         torch.cuda.synchronize()
         algo = {"down_fwd": E * T * d_in, "up_fwd": 2 * E * T * d_out, "up_bwd(g only)": E * T * d_out, "up_bwd(dB only)": E * T * d_out, "up_bwd(g+dB)": E * T * d_out,
                 "down_bwd(dA only)": E * T * d_in, "down_bwd(dx only)": 2 * E * T * d_in, "cross_fwd": 0, "cross_bwd": 0}
-        sweeps = {
-            "down_fwd": [("xa_ng", v) for v in (2, 4, 8)],
-            "up_fwd": [("expand_depth", 3)] + [("expand_bpc", v) for v in (2, 4, 8, 12, 16)],
-            "down_bwd(dx only)": [("expand_depth", 2)] + [("expand_bpc", v) for v in (2, 4, 8)],
-            "up_bwd(g+dB)": [("gy_ng", v) for v in (4, 8, 16)],
-            "up_bwd(g only)": [("gy_ng", v) for v in (4, 8, 16)],
-            "down_bwd(dA only)": [("wgrad_bpc", v) for v in (1, 2, 3, 4, 6, 8)],
-        }
         print(f"\n=== {d_in} -> {d_out}  (T={T}) ===")
         for name, fn in cs.items():
             if only and only not in name:
                 continue
             base = timeit(fn)
             gb = algo[name] / (base * 1e-6) / 1e9 if algo[name] else 0
-            print(f"{name:20s} default            {base:8.1f} us  {gb:7.0f} GB/s algorithmic")
-            for key, val in ([] if os.environ.get("SWEEP") == "0" else sweeps.get(name, [])):
-                lib.moka_tune(key.encode(), val)
-                t = timeit(fn)
-                lib.moka_tune(key.encode(), 0)
-                gb = algo[name] / (t * 1e-6) / 1e9 if algo[name] else 0
-                print(f"{'':20s} {key:12s}={val:<4d} {t:8.1f} us  {gb:7.0f} GB/s")
+            print(f"{name:20s} {base:8.1f} us  {gb:7.0f} GB/s algorithmic")
         del w, cs
         torch.cuda.empty_cache()
 
